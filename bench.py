@@ -11,9 +11,13 @@ parallel wq/wk/wv/gate/up, row-parallel wo/down with an RCCL all-reduce of the f
 (csrc/tp.cpp); one token stream, so "scaling" is "strong".  torch is used for plumbing only (rendezvous, barrier,
 max-reduce of the timings, torch.cuda.synchronize()).
 
-Extra objects on the JSON line: "roofline" (dominant kernel class, hipEvent-timed on the backend's own stream in a
-separate eager pass of the same decode steps; algorithmic bytes = the weight bytes each launch streams) and
-"cpu_baseline" (the CPU oracle = our restatement of ggml-cpu, kind "port", timed on this host's cores, rank 0, N=1).
+A plain run sets up, warms up, times the K steps and prints the line.  With --full the line also carries "roofline"
+(dominant kernel class, hipEvent-timed on the backend's own stream in a separate eager pass of the same decode steps, then
+rocprofv3 passes of their own; algorithmic bytes = the weight bytes each launch streams), "kernel_classes_us",
+"cpu_baseline" (the CPU oracle = our restatement of ggml-cpu, kind "port", timed on this host's cores, rank 0, N=1) with
+"parity" (the timed model's logits against it) and, for tensor-split runs, "allreduce_us" and the replica leg.
+
+--dump-outputs DIR writes the logits of the last timed step (what llama_get_logits hands the caller) to DIR/logits.npy.
 """
 import argparse
 import json
@@ -130,6 +134,20 @@ def rocprof_kernel_us(symbol, args):
         shutil.rmtree(out, ignore_errors=True)
 
 
+def dump_logits(ctx, out_dir, name, max_bytes=64 << 20):
+    """The logits the last llama_decode of `ctx` handed its caller (llama_get_logits: one float32 row of the vocabulary per output) as
+    out_dir/<name>.npy.  Past `max_bytes`, a fixed, seeded sample of the rows in their original order."""
+    import numpy as np
+    H = ctx.H
+    n_out = int(H.llm_n_outputs(ctx.c))
+    lg = np.ctypeslib.as_array(H.llm_get_logits(ctx.c), shape=(n_out, ctx.model.n_vocab_local))
+    keep = max(1, max_bytes // lg[0].nbytes)
+    if n_out > keep:
+        lg = lg[np.sort(np.random.default_rng(0).choice(n_out, keep, replace=False))]
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(lg, dtype=np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -158,7 +176,15 @@ def main():
     ap.add_argument("--cpu-steps", type=int, default=32)
     ap.add_argument("--timing-steps", type=int, default=16)
     ap.add_argument("--pmc-traffic", type=int, default=1, help="1: re-run a short decode under rocprofv3 --pmc FETCH_SIZE (own pass) for roofline.traffic")
+    ap.add_argument("--full", action="store_true", help="also run what the headline does not need: the per-kernel timing pass and the rocprofv3 passes of `roofline`, the CPU "
+                                                        "baseline and the parity check against it, the replica leg of tensor-split runs (--timing-steps, --pmc-traffic, "
+                                                        "--no-cpu-baseline, --cpu-steps and --replica-leg act inside it)")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", metavar="DIR", help="write the logits of the last timed step to DIR/logits.npy (float32, one row per output of "
+                                                                              "the step; DIR/logits_rank<r>.npy per rank with --gpus N > 1; a fixed, seeded sample of the rows "
+                                                                              "beyond 64 MB)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` on its own: start the N ranks ourselves, exactly as the driver's multi-GPU line does (one process
@@ -359,7 +385,8 @@ def main():
 
     def leg():  # W untimed warm-up steps, then exactly K timed steps between barrier + synchronize; max over ranks
         nonlocal pos
-        steps(args.warmup)
+        if args.warmup:  # (the host library refuses a call of zero steps)
+            steps(args.warmup)
         pos += args.warmup
         g0 = be.stat("graph_launches")
         gl0 = be.stat("graph_launch_host_ns")
@@ -459,48 +486,51 @@ def main():
     streams = 1 if tp_size > 1 or world == 1 else world
     tok_s = streams * args.np * args.steps / elapsed  # (sequence-steps per second: what the byte accounting below multiplies by)
     host_split = [x / max(1, args.steps) for x in ctx.timings()]
+    if args.dump_outputs:  # before anything else decodes on this context: its logits are still the last timed step's
+        dump_logits(ctx, args.dump_outputs, "logits" if world == 1 else f"logits_rank{rank}")
 
-    # ---- per-kernel-class timing pass (eager, hipEvents on the backend's stream)
+    # ---- per-kernel-class timing pass (eager, hipEvents on the backend's stream) and the rocprofv3 passes of the roofline: --full only
     roofline = None
     classes = {}
-    try:
-        be.set_option("timing", 1)
-        for i in range(args.timing_steps):
-            step(i)
-        classes = be.timing_report()
-        be.set_option("timing", 0)
-        pos += args.timing_steps
-        classes.pop("_bracket_noop", None)
-        mm = {k: v for k, v in classes.items() if k.startswith("mmvq") or k.startswith("mmq")}
-        if mm:
-            dom = max(mm, key=lambda k: mm[k][1])
-            cnt, ms, nbytes = mm[dom]
-            # the streaming mat-vec launches carry their own start/stop events (hipExtLaunchKernelGGL: the dispatch packet's
-            # begin/end timestamps, what rocprofv3 reads too), so this is the kernel's duration, not a host-side bracket
-            avg_us = ms * 1e3 / cnt
-            ach = nbytes / cnt / (avg_us * 1e-6) / 1e9
-            roofline = {"bound": "hbm", "kernel": dom, "achieved": round(ach, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(ach / HBM_PEAK_GBS, 4),
-                        "traffic": None, "launches": cnt, "avg_us": round(avg_us, 2), "alg_bytes_per_launch": round(nbytes / cnt),
-                        "timing": "per-launch start/stop hipEvents (hipExtLaunchKernelGGL) on the backend stream, eager pass of the same decode steps"}
-    except Exception as e:
-        roofline = {"error": str(e)}
-    if roofline and "kernel" in roofline and args.pmc_traffic and rank == 0 and world == 1 and not os.environ.get("BENCH_PMC_CHILD"):
-        sym = _class_to_symbol(roofline["kernel"], args.np, planes=int(be.stat("decode_copy_launches")) > 0, short_rows=(hp.n_embd % 2048) != 0)
-        if sym:
-            torch.cuda.synchronize()
-            tr, how = pmc_traffic(sym, args)
-            roofline["traffic"] = round(tr) if tr else None
-            roofline["traffic_source"] = how
-            # `frac` from the duration rocprofv3 reports for the kernel (what profiles/ holds); the in-process per-launch events beside it
-            us, n_l, how_t = rocprof_kernel_us(sym, args)
-            roofline["frac_hipevent"], roofline["avg_us_hipevent"] = roofline["frac"], roofline["avg_us"]
-            if us:
-                ach_r = roofline["alg_bytes_per_launch"] / (us * 1e-6) / 1e9
-                roofline.update({"achieved": round(ach_r, 1), "frac": round(ach_r / HBM_PEAK_GBS, 4), "frac_rocprof": round(ach_r / HBM_PEAK_GBS, 4), "avg_us": round(us, 2), "avg_us_rocprof": round(us, 2),
-                                 "timing": how_t + "; *_hipevent: per-launch start/stop hipEvents (hipExtLaunchKernelGGL) on the backend stream, eager pass of the same decode steps"})
-            else:
-                roofline["frac_rocprof"] = None
-                roofline["timing"] += f" [rocprofv3 pass unavailable: {how_t}]"
+    if args.full:
+        try:
+            be.set_option("timing", 1)
+            for i in range(args.timing_steps):
+                step(i)
+            classes = be.timing_report()
+            be.set_option("timing", 0)
+            pos += args.timing_steps
+            classes.pop("_bracket_noop", None)
+            mm = {k: v for k, v in classes.items() if k.startswith("mmvq") or k.startswith("mmq")}
+            if mm:
+                dom = max(mm, key=lambda k: mm[k][1])
+                cnt, ms, nbytes = mm[dom]
+                # the streaming mat-vec launches carry their own start/stop events (hipExtLaunchKernelGGL: the dispatch packet's
+                # begin/end timestamps, what rocprofv3 reads too), so this is the kernel's duration, not a host-side bracket
+                avg_us = ms * 1e3 / cnt
+                ach = nbytes / cnt / (avg_us * 1e-6) / 1e9
+                roofline = {"bound": "hbm", "kernel": dom, "achieved": round(ach, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(ach / HBM_PEAK_GBS, 4),
+                            "traffic": None, "launches": cnt, "avg_us": round(avg_us, 2), "alg_bytes_per_launch": round(nbytes / cnt),
+                            "timing": "per-launch start/stop hipEvents (hipExtLaunchKernelGGL) on the backend stream, eager pass of the same decode steps"}
+        except Exception as e:
+            roofline = {"error": str(e)}
+        if roofline and "kernel" in roofline and args.pmc_traffic and rank == 0 and world == 1 and not os.environ.get("BENCH_PMC_CHILD"):
+            sym = _class_to_symbol(roofline["kernel"], args.np, planes=int(be.stat("decode_copy_launches")) > 0, short_rows=(hp.n_embd % 2048) != 0)
+            if sym:
+                torch.cuda.synchronize()
+                tr, how = pmc_traffic(sym, args)
+                roofline["traffic"] = round(tr) if tr else None
+                roofline["traffic_source"] = how
+                # `frac` from the duration rocprofv3 reports for the kernel (what profiles/ holds); the in-process per-launch events beside it
+                us, n_l, how_t = rocprof_kernel_us(sym, args)
+                roofline["frac_hipevent"], roofline["avg_us_hipevent"] = roofline["frac"], roofline["avg_us"]
+                if us:
+                    ach_r = roofline["alg_bytes_per_launch"] / (us * 1e-6) / 1e9
+                    roofline.update({"achieved": round(ach_r, 1), "frac": round(ach_r / HBM_PEAK_GBS, 4), "frac_rocprof": round(ach_r / HBM_PEAK_GBS, 4), "avg_us": round(us, 2), "avg_us_rocprof": round(us, 2),
+                                     "timing": how_t + "; *_hipevent: per-launch start/stop hipEvents (hipExtLaunchKernelGGL) on the backend stream, eager pass of the same decode steps"})
+                else:
+                    roofline["frac_rocprof"] = None
+                    roofline["timing"] += f" [rocprofv3 pass unavailable: {how_t}]"
 
     # ---- tensor-split runs: the same decode with ONE process driving the N devices — llama-box is a single process (engine.cpp:87-95): -sm row -ts 1,1,...
     # reaches "ggml_backend_split_buffer_type", whose graphs the backend runs as tensor parallelism over its own devices (csrc/tp_inproc.cpp: sharded
@@ -535,7 +565,8 @@ def main():
                         if extra_leg:  # the same cache depth as the one-process-per-GPU leg it is compared with (that one ran its eager leg first): ADVICE r05
                             assert c_ip.decode_steps([[int(toks[p_ip + i])] for i in range(extra_leg)], 1, p_ip) == 0
                             p_ip += extra_leg
-                        assert c_ip.decode_steps([[int(toks[p_ip + i])] for i in range(args.warmup)], 1, p_ip) == 0
+                        if args.warmup:
+                            assert c_ip.decode_steps([[int(toks[p_ip + i])] for i in range(args.warmup)], 1, p_ip) == 0
                         p_ip += args.warmup
                         g0_, a0_ = be_ip.stat("graph_launches"), be_ip.stat("allreduces")
                         be_ip.synchronize()
@@ -571,7 +602,7 @@ def main():
     # are worth as N data-parallel engines is the other half of the picture.  Informational: `value` stays the tensor-split number.
     w_bytes = model.stream_bytes()
     replicas = None
-    if (tp_size > 1 and not emulated and args.replica_leg) or (world > 1 and args.replica_leg == 2):  # (2: exercise the leg in the single-GPU dry run)
+    if args.full and ((tp_size > 1 and not emulated and args.replica_leg) or (world > 1 and args.replica_leg == 2)):  # (2: exercise the leg in the single-GPU dry run)
         try:
             ctx.free(); model.free()
             ctx = model = None
@@ -581,7 +612,8 @@ def main():
                 rc, _ = ctx_r.decode(toks[:args.prefill], range(args.prefill), want=[0] * (args.prefill - 1) + [1])
                 assert rc == 0
             rows_w = [[int(toks[args.prefill + i])] for i in range(args.warmup)]
-            assert ctx_r.decode_steps(rows_w, 1, args.prefill) == 0
+            if rows_w:
+                assert ctx_r.decode_steps(rows_w, 1, args.prefill) == 0
             rows_t = [[int(toks[args.prefill + args.warmup + i])] for i in range(args.steps)]
             sync()
             tr0 = time.perf_counter()
@@ -599,7 +631,7 @@ def main():
     # ---- CPU baseline: the oracle (restated ggml-cpu), same model shape, on this host's cores
     cpu_baseline = None
     parity = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         try:
             import ctypes as C
             import shutil

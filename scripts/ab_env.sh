@@ -6,7 +6,7 @@ VALS=(); while [ $# -gt 0 ] && [ "$1" != "--" ]; do VALS+=("$1"); shift; done; [
 python bench.py --no-cpu-baseline --pmc-traffic 0 --timing-steps 0 --steps 32 "$@" > /dev/null 2>&1  # discarded warm-up
 for rep in 1 2; do
   for v in "${VALS[@]}"; do
-    env $VAR=$v python bench.py --no-cpu-baseline --pmc-traffic 0 --timing-steps 16 --steps 64 "$@" 2>/dev/null | python3 -c "
+    env $VAR=$v python bench.py --full --no-cpu-baseline --pmc-traffic 0 --timing-steps 16 --steps 64 "$@" 2>/dev/null | python3 -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 k = d.get('kernel_classes_us', {})

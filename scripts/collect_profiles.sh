@@ -9,7 +9,7 @@ rm -f gpurun_out/parity_log.txt
 timeout 1200 python -m pytest tests -m gpu -q -p no:cacheprovider > $O/pytest_gpu.log 2>&1; echo "pytest rc=$?"; tail -n 2 $O/pytest_gpu.log
 cp gpurun_out/parity_log.txt $O/parity_log.txt 2>/dev/null
 timeout 300 python __graft_entry__.py smoke > $O/smoke.log 2>&1; echo "smoke rc=$?"
-timeout 900 python bench.py > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"; tail -c 1600 $O/bench.json
+timeout 900 python bench.py --full > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"; tail -c 1600 $O/bench.json
 rm -rf gpurun_out/prof
 timeout 600 rocprofv3 --kernel-trace --stats -d gpurun_out/prof -o bench -- python bench.py --no-cpu-baseline --pmc-traffic 0 > $O/bench_under_rocprof.json 2> $O/prof.err; echo "rocprof rc=$?"
 python scripts/prof_summary.py gpurun_out/prof/bench_results.db > $O/bench_kernel_stats.csv; head -n 16 $O/bench_kernel_stats.csv | cut -c1-150

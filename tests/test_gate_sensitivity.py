@@ -33,7 +33,7 @@ def _rows(mc, prompt, fast, variant):
         lib.oracle_set_fast(0)
 
 
-def test_the_bar_as_written_trips_on_an_output_path_error_and_passes_a_correct_second_implementation():
+def test_the_bar_as_written_trips_on_an_output_path_error_and_passes_a_correct_second_implementation(built):
     H = L.host()
     hp = preset("llama3-8b-q4_k_m-damped", n_layer=4, n_vocab=8192)  # Llama-3-8B's layer shapes, formats and damped branch gain (0.01); 4 layers, 8 k vocabulary: ~1 GB
     rng = np.random.default_rng(5)

@@ -653,6 +653,26 @@ def test_bench_two_ranks_dry_run_on_one_gpu(plog):
     assert ip["allreduces_per_step"] == 2 * 2, ip
 
 
+@pytest.mark.gpu
+def test_bench_plain_run_is_the_headline_and_dumps_the_last_steps_logits(built, tmp_path):
+    """A plain `bench.py` run times its steps and prints the line without the timing pass, the rocprofv3 passes or the CPU leg (those come with
+    --full); --dump-outputs writes what the last timed step handed the caller: one float32 row of logits per sequence."""
+    import json
+    import subprocess
+    import sys
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--prefill", "64", "--layers", "2", "--np", "2",
+                        "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{") and '"metric"' in ln]
+    assert len(lines) == 1, r.stdout[-1500:]
+    out = json.loads(lines[0])
+    assert out["steps"] == 3 and out["warmup"] == 1 and out["ms_per_step"] > 0 and out["value"] > 0
+    assert out["roofline"] is None and out["cpu_baseline"] is None and out["parity"] is None and out["kernel_classes_us"] == {}
+    lg = np.load(tmp_path / "logits.npy")
+    assert lg.dtype == np.float32 and lg.shape == (2, preset("llama3-8b-q4_k_m").n_vocab) and np.all(np.isfinite(lg)) and np.any(lg != 0)
+
+
 _SOFT_FAIL_WORKER = r'''
 import ctypes as C, os, sys
 import numpy as np

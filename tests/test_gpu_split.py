@@ -134,7 +134,7 @@ def test_llama3_70b_shard_shapes_on_eight_logical_devices(plog, fa, threads, ord
     assert 0.0 <= ip["nmse_after_host_write_vs_one_device"] <= 1e-3 and ip["kv_scatters_total"] == 2, ip
 
 
-def test_split_rows_planning_without_a_device():
+def test_split_rows_planning_without_a_device(built):
     """The row plan is host arithmetic: reachable through the registration's proc address on a box without any GPU."""
     import ctypes as C
 

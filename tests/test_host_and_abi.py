@@ -340,7 +340,7 @@ def test_rope_multi_oracle_against_closed_form(H):
         _rope_multi_oracle(H, x, pos4, HD, [0, 0, 0, 0], L.ROPE_MROPE)
 
 
-def test_logits_ith_and_host_sampler_mirrors():
+def test_logits_ith_and_host_sampler_mirrors(built):
     """llama_get_logits_ith semantics (batch position / negative = from the end / NULL without logits) and the two host-side
     consumers the reference runs on those rows: common_sampler_sample2 with a greedy chain (sampling.patch:58-81, called at
     httpserver.hpp:4294) and get_token_probabilities (httpserver.hpp:440-467) — here over the CPU oracle."""
@@ -411,7 +411,36 @@ def test_bench_gpus_n_starts_n_ranks_itself_and_fails_without_gpus():
     assert "refusing to run" in r.stderr  # came from the ranks torch.distributed.run started, not from the parent
 
 
-def test_graph_key_decides_what_a_captured_graph_stands_for():
+def test_bench_refuses_a_run_without_timed_steps():
+    """`--steps` is the number of timed steps and `ms_per_step` is divided by it: zero steps (or a negative warm-up) is refused before anything starts."""
+    for args in (["--steps", "0"], ["--steps", "4", "--warmup", "-1"]):
+        r = _run_bench(args, timeout=120)
+        assert r.returncode == 2 and "--steps must be >= 1" in r.stderr, (args, r.returncode, r.stderr[-500:])
+        assert "{" not in r.stdout
+
+
+def test_bench_dump_writes_the_callers_logits_and_samples_rows_past_the_cap(tmp_path):
+    """--dump-outputs: the rows llama_get_logits hands the caller, float32, as <dir>/<name>.npy; past the size cap a fixed, seeded sample of the rows
+    in their original order (the same rows on every run, so that two builds compare row for row)."""
+    import types
+
+    import bench
+    nv, n_out = 64, 10
+    buf = (C.c_float * (n_out * nv))(*np.arange(n_out * nv, dtype=np.float32))
+    H = types.SimpleNamespace(llm_n_outputs=lambda c: n_out, llm_get_logits=lambda c: C.cast(buf, C.POINTER(C.c_float)))
+    ctx = types.SimpleNamespace(H=H, c=None, model=types.SimpleNamespace(n_vocab_local=nv))
+    bench.dump_logits(ctx, str(tmp_path / "all"), "logits")
+    full = np.load(tmp_path / "all" / "logits.npy")
+    assert full.dtype == np.float32 and full.shape == (n_out, nv) and np.array_equal(full.ravel(), np.arange(n_out * nv, dtype=np.float32))
+    for d in ("a", "b"):
+        bench.dump_logits(ctx, str(tmp_path / d), "logits", max_bytes=4 * nv * 4)
+    a, b = np.load(tmp_path / "a" / "logits.npy"), np.load(tmp_path / "b" / "logits.npy")
+    assert a.shape == (4, nv) and np.array_equal(a, b)
+    rows = (a[:, 0] / nv).astype(int)
+    assert np.all(np.diff(rows) > 0) and np.array_equal(a, full[rows])
+
+
+def test_graph_key_decides_what_a_captured_graph_stands_for(built):
     """graph.cpp: a captured hipGraph is replayed for a graph whose KEY — per node {type, op, ne, nb, op_params, flags, buffer, data, which sources,
     mask-content hint}, per source {type, buffer, ne, nb, data} — equals the one it was captured for; since round 5 the key of the graph replayed
     last is compared in place (no hash: a collision cannot replay another graph, and no 240 KB byte-serial FNV before every step).  Host arithmetic,
