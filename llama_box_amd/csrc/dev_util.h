@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cfloat>
 #include <cstdint>
 
 namespace mi355x {
@@ -128,10 +129,14 @@ template <typename Q8K> __device__ __forceinline__ void wave_quantize_q8_K(const
         const int first = __ffsll((long long) hit) - 1;
         const float mx = readlane_f32(mx_l, first);
         iscale = -127.f / mx;
+        // (max an f32 subnormal: 127 / |max| overflows to inf, the products are +-inf / NaN, and the CPU's nearest_int() leaves every quant 0
+        // under d = 1 / inf = 0.  A saturating float -> int conversion here would put INT_MIN into the bsums: -inf in f16, and 0 * -inf = NaN downstream)
+        if (fabsf(iscale) <= FLT_MAX) {
 #pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const int r = (int) rintf(iscale * v[k]);  // round-half-even == ggml's nearest_int()
-            q[k] = r < 127 ? r : 127;
+            for (int k = 0; k < 4; ++k) {
+                const int r = (int) rintf(iscale * v[k]);  // round-half-even == ggml's nearest_int()
+                q[k] = r < 127 ? r : 127;
+            }
         }
     }
     const uint32_t packed = (uint32_t) (q[0] & 0xFF) | ((uint32_t) (q[1] & 0xFF) << 8) | ((uint32_t) (q[2] & 0xFF) << 16) | ((uint32_t) (q[3] & 0xFF) << 24);

@@ -18,6 +18,7 @@ import pytest
 
 import harness as T
 import llama_box_amd as L
+import probes as P
 from model_util import Context, Model, preset
 
 pytestmark = pytest.mark.gpu
@@ -56,6 +57,11 @@ def edge_rows(rng, n_rows, width):
     x[3, :32] = (np.arange(32, dtype=np.float32) - 15.5) * 0.25  # values that land on .5 before the truncation
     x[4, :32] = np.where(np.arange(32) % 2 == 0, 1e-20, -1e-20).astype(np.float32)  # under iq4_nl's group epsilon
     x[5, :] = np.where(rng.integers(0, 2, width) == 0, 0.0, -0.0).astype(np.float32)  # zeros of both signs: which zero the scale / minimum inherits is part of the bytes
+    # the half-way-everywhere and negative-first-tie blocks of the activation catalogue (tests/probes.py), each in a block of its own
+    planted = dict(P.edge_blocks("q8_0", rng))
+    for i, name in enumerate(("halfway_max_pos", "halfway_max_neg", "tie_neg_first_far", "tie_neg_first_quad")):
+        at = (3 * i + 1) % (width // 32)
+        x[6 + i, 32 * at:32 * at + 32] = planted[name]
     return x
 
 
