@@ -1830,7 +1830,11 @@ static int run_node(exec_state & st, int i) {
                 if (o1) {
                     ggml_tensor * a2 = next(2);
                     const ggml_tensor * o2 = (a2 && single_use(st, a1)) ? add_partner(a2, a1) : nullptr;
-                    if (o2) {
+                    // (columns that belong to the matrix-core kernel — two of a Q4_K / Q6_K matrix — keep it: its store takes ONE addend, so the second ADD stays a
+                    // node of its own.  With both addends the product fell back to the mat-vec kernel, and which kernel — which f32 summation order — a mat-mul got
+                    // depended on whether its ADDs happened to follow it directly in the node list)
+                    const bool to_mmq = M >= mmq_min_cols_for(c, a->type) && c->opt.mmq_i8 && mmq_i8_supported(a->type, a->ne[0], a->ne[1], M);
+                    if (o2 && !to_mmq) {
                         if (!run_mul_mat_q(st, a, nullptr, b, a2, o1, o2)) return -1;
                         c->st.fused_nodes += 2;
                         return 3;

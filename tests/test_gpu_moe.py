@@ -1,5 +1,7 @@
 """Mixture-of-experts FFN blocks on the MI355X: MUL_MAT_ID (csrc/mmid.hip), the router ops ARGSORT / SUM_ROWS / CLAMP, batched GET_ROWS, the 3-D split
-SwiGLU, the whole build_moe_ffn sequence, its hipGraph capture, out-of-range ids, and a guard on the dense paths.  References: tests/moe_ref.py."""
+SwiGLU, the whole build_moe_ffn sequence, its hipGraph capture, out-of-range ids, and a guard on the dense paths.  References: tests/moe_ref.py.
+The edge cases — the kernel forms these model shapes never select, strided and offset operands, the exact read-back of the quantiser in front of MUL_MAT_ID and a layer
+with a shared expert — live in tests/test_gpu_moe_edges.py."""
 import ctypes as C
 
 import numpy as np

@@ -20,6 +20,7 @@
     attention -> wo: fa_wo prologue (flash_attn_fat + attnpro)   test_attention_hands_its_result_to_wo_quantised[fa_wo_prologue-*]
     attention -> wo: Q8_K blocks from the single pass / combine  test_attention_hands_its_result_to_wo_quantised[q8out_single_pass-*], [q8out_combine-*]
     per-block indexing over six super-blocks (K = 1536)          test_block_indexing_over_six_super_blocks
+    launch_quantize_act on a 3-D b -> k_mmid (MUL_MAT_ID)        tests/test_gpu_moe_edges.py: test_quantiser_read_back_through_mul_mat_id
     (k_mmq_wide serves Q4_K / Q5_K only — mmq_skinny.hip — hence no Q6_K case of test_k_quant_wide_form.)
 
     Left out, with the reason (two routes):

@@ -167,3 +167,80 @@ def test_composite_block_reference_matches_numpy_f64(built):
     e = T.nmse(out, f64)
     print(f"block reference vs NumPy f64: nmse={e:.3e}")
     assert e <= 5e-3
+
+
+# ------------------------------------------------------------------------------------------------ helpers of tests/test_gpu_moe_edges.py
+def test_kernel_selection_thresholds_are_read_from_the_source(built):
+    """moe_ref.mmid_limits parses every threshold out of launch_mmid / launch_mmid_t / mm_id_ok; the shapes derived from them sit on the right side of each."""
+    lim = M.mmid_limits()
+    print(f"mmid limits: {lim}")
+    assert lim["r2_min"] > 0 and lim["pair_max"] > 0 and lim["vec_align"] in (4, 8, 16, 32) and lim["vec_k"] >= 2
+    for qt in (L.Q4_K, L.Q5_K, L.Q6_K, L.Q8_0):
+        K = M.lds_free_k(qt, lim)
+        per = lim["act_bytes"]["q8_0" if qt == L.Q8_0 else "q8_K"]
+        nblk = K // L.TYPE_BLCK[qt]
+        print(f"  type {qt}: the LDS-free form starts at K = {K} ({nblk} activation blocks of {per} bytes)")
+        assert K % L.TYPE_BLCK[qt] == 0 and nblk * per > lim["lds_max"] >= (nblk - 1) * per
+
+
+@pytest.mark.parametrize("qtype", [L.Q4_K, L.Q5_K, L.Q6_K, L.Q8_0], ids=["q4_K", "q5_K", "q6_K", "q8_0"])
+@pytest.mark.parametrize("K", [512, 1536])
+def test_readout_experts_oracle_equals_the_numpy_twin(built, qtype, K):
+    """The CPU half of the exact read-back through MUL_MAT_ID: the composite oracle over the stacked, rotated read-out experts equals the NumPy twin of the
+    activation quantiser bit for bit (+-0 equal, NaN where the twin has NaN) — one row per (slot, token) and one row per token, 1 / 3 / 32 tokens."""
+    import probes as P
+    for what in ("values", "bsums") if qtype in (L.Q4_K, L.Q5_K) else ("values",):
+        for per_slot in (True, False):
+            cases = [M.readout_case(qtype, K, n_tok, per_slot, what) for n_tok in (1, 3, 32)]
+            W = cases[0][0]
+            ref = M.mmid_reference(qtype, W, K, W.shape[1], [(b, ids) for _, b, ids, _ in cases], 4)
+            for (_, b, ids, want), r in zip(cases, ref):
+                bad = P.bits(r) != P.bits(want)
+                assert not bad.any(), f"{what} per_slot={per_slot} n_tokens={ids.shape[0]}: {int(bad.sum())}/{bad.size} outputs differ; first at {np.argwhere(bad)[0].tolist()}"
+    # the rotation tells the experts apart: another expert's read-out of the same row is a different vector
+    W, b, ids, want = M.readout_case(qtype, K, 3, True)
+    _, shifts = M.readout_experts(qtype, K, 4)
+    wrong = M.expected_expert_readout(qtype, b, (ids + 1) % 4, shifts)
+    assert all((P.bits(wrong[t, s]) != P.bits(want[t, s])).any() for t in range(3) for s in range(2))
+
+
+SHARED_LAYERS = {
+    # routed up / gate, routed down, shared up / gate, shared down
+    "q4_K+q6_K": (L.Q4_K, L.Q6_K, L.Q4_K, L.Q6_K),
+    "q8_0": (L.Q8_0, L.Q8_0, L.Q8_0, L.Q8_0),
+    "routed-q4_K-shared-q8_0": (L.Q4_K, L.Q4_K, L.Q8_0, L.Q8_0),
+}
+
+
+@pytest.mark.parametrize("name", sorted(SHARED_LAYERS))
+def test_shared_expert_layer_reference_matches_numpy_f64_and_its_two_orders_differ(built, name):
+    """SharedExpertLayer.reference (oracle ops + NumPy glue) against the layer in float64 on de-quantised weights; and the two build orders give
+    different node lists with the same multiset of ops."""
+    tu, td, su, sd = SHARED_LAYERS[name]
+    lay = M.SharedExpertLayer(512, 768, 1024, 8, 2, tu, td, su, sd, seed=3)
+    x = lay.inputs(5, np.random.default_rng(9))
+    out, ids, probs, prods = lay.reference(x, 4)
+    srt = np.sort(probs, axis=1)[:, ::-1]
+    assert np.all(srt[:, 1] - srt[:, 2] > 1e-3 * srt[:, 1])
+    e = T.nmse(out, lay.numpy_f64(x, ids))
+    print(f"shared-expert layer {name}: reference vs NumPy f64 nmse = {e:.3e}")
+    assert e <= 5e-3
+    assert [p.shape for p in prods] == [(5, 2, 768), (5, 2, 768), (5, 2, 512)]
+    ops = {}
+    for order in lay.ORDERS:
+        g = T.G("oracle")
+        try:
+            o, sel, _, _, first = lay.build(g, x, order)
+            ops[order] = M.node_ops(g, [o, sel], first)
+        finally:
+            g.free()
+    a, b, c = (ops[o] for o in lay.ORDERS)
+    mm, mmid = _op_number(L.host(), "MUL_MAT"), _op_number(L.host(), "MUL_MAT_ID")
+    assert a != b and sorted(a) == sorted(b)
+    first_of = lambda seq, op: seq.index(op)  # noqa: E731
+    # routed_first: the router MUL_MAT, then the three MUL_MAT_IDs, then the dense chain; shared_first: the three dense MUL_MATs before the first MUL_MAT_ID
+    assert [o for o in a if o in (mm, mmid)] == [mm, mmid, mmid, mmid, mm, mm, mm]
+    assert [o for o in b if o in (mm, mmid)] == [mm, mm, mm, mm, mmid, mmid, mmid]
+    # shared_up_gate_first: the dense gate and up products, the router, the MUL_MAT_IDs directly behind it, the dense down product last
+    assert [o for o in c if o in (mm, mmid)] == [mm, mm, mm, mmid, mmid, mmid, mm] and sorted(c) == sorted(a)
+    assert first_of(a, mmid) < len(a) and first_of(b, mmid) > first_of(b, mm)
