@@ -1562,6 +1562,21 @@ static enum ggml_status op_argmax(struct ggml_tensor * dst) {
     return GGML_STATUS_SUCCESS;
 }
 
+/* CLAMP: ggml_compute_forward_clamp_f32 — y = MAX(MIN(x, max), min) with the comparison macros' `a < b ? a : b` (a NaN becomes max); contiguous f32, in place */
+static enum ggml_status op_clamp(struct ggml_tensor * dst) {
+    const struct ggml_tensor * a = dst->src[0];
+    if (a->type != GGML_TYPE_F32 || dst->type != GGML_TYPE_F32 || !ggml_abi_is_contiguous(a) || !ggml_abi_is_contiguous(dst)) return GGML_STATUS_FAILED;
+    const float lo = op_f32(dst, 0), hi = op_f32(dst, 1);
+    const int64_t n = ggml_abi_nelements(a);
+    const float * x = (const float *) a->data;
+    float * y = (float *) dst->data;
+    for (int64_t i = 0; i < n; ++i) {
+        const float m = x[i] < hi ? x[i] : hi;
+        y[i] = m > lo ? m : lo;
+    }
+    return GGML_STATUS_SUCCESS;
+}
+
 /* ------------------------------------------------------------------------------------------ */
 int oracle_supports_op(const struct ggml_tensor * node) {
     switch (node->op) {
@@ -1569,7 +1584,7 @@ int oracle_supports_op(const struct ggml_tensor * node) {
         case GGML_OP_MUL_MAT: case GGML_OP_ADD: case GGML_OP_SUB: case GGML_OP_MUL: case GGML_OP_DIV:
         case GGML_OP_SCALE: case GGML_OP_RMS_NORM: case GGML_OP_UNARY: case GGML_OP_GLU: case GGML_OP_GET_ROWS:
         case GGML_OP_SET_ROWS: case GGML_OP_CPY: case GGML_OP_DUP: case GGML_OP_CONT: case GGML_OP_SOFT_MAX:
-        case GGML_OP_ROPE: case GGML_OP_FLASH_ATTN_EXT: case GGML_OP_ARGMAX:
+        case GGML_OP_ROPE: case GGML_OP_FLASH_ATTN_EXT: case GGML_OP_ARGMAX: case GGML_OP_CLAMP:
             return 1;
         default: return 0;
     }
@@ -1596,6 +1611,7 @@ enum ggml_status oracle_compute_node(struct ggml_tensor * node, int n_threads) {
         case GGML_OP_ROPE: return op_rope(node);
         case GGML_OP_FLASH_ATTN_EXT: return op_flash_attn_ext(node, nth);
         case GGML_OP_ARGMAX: return op_argmax(node);
+        case GGML_OP_CLAMP: return op_clamp(node);
         default: return GGML_STATUS_FAILED;
     }
 }

@@ -31,7 +31,8 @@ def build_oracle():
 def oracle():
     global _oracle
     if _oracle is None:
-        if not os.path.exists(ORACLE_SO):
+        srcs = [os.path.join(ORACLE_DIR, f) for f in ("ggml_cpu_ref.c", "oracle.h", "Makefile")]
+        if not os.path.exists(ORACLE_SO) or os.path.getmtime(ORACLE_SO) < max(os.path.getmtime(f) for f in srcs):  # (a library older than its source lacks the newer ops)
             build_oracle()
         lib = C.CDLL(ORACLE_SO)
         lib.oracle_graph_compute.restype = C.c_int

@@ -1,6 +1,6 @@
 """Helpers for the mixture-of-experts tests: graph builders for llama.cpp's build_moe_ffn sequence and its COMPOSITE reference.
 
-The oracle has no MUL_MAT_ID / ARGSORT / SUM_ROWS / CLAMP, so the reference is composed from what it has.  ggml-cpu's mul_mat_id is
+The oracle has no MUL_MAT_ID / ARGSORT / SUM_ROWS (and had no CLAMP when this was written), so the reference is composed from what it has.  ggml-cpu's mul_mat_id is
 one vec_dot per (row, slot, token) over that pair's quantised activation row; the oracle's MUL_MAT is the same vec_dot per (row, column),
 each column quantised on its own (oracle/ggml_cpu_ref.c: op_mul_mat) — so the product of a (slot, token) pair is a ONE-column MUL_MAT of
 the selected expert's 2-D slice (`ggml_view_2d(as, K, N, nb1, id * nb2)`) with that pair's activation row, the ids taken from NumPy.
