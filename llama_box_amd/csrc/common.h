@@ -103,6 +103,14 @@ struct q80_dev {
     float d;
 };
 static_assert(sizeof(q80_dev) == 36, "q80_dev");
+// Q8_1-quantised activation block for Q4_1 / Q5_1 weights: a q80_dev plus block_q8_1.s = f16(sum(qs) * d) taken with the UNROUNDED d = amax / 127, as
+// quantize_row_q8_1_ref does — it cannot be rebuilt from the stored (f16-rounded) d, so the quantiser emits it
+struct q81_dev {
+    int8_t qs[32];
+    float d;
+    float s;
+};
+static_assert(sizeof(q81_dev) == 40, "q81_dev");
 
 struct backend_ctx;
 

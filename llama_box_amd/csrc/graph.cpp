@@ -16,7 +16,15 @@
 
 namespace mi355x {
 
-static bool is_quant(int t) { return t == GGML_TYPE_Q4_K || t == GGML_TYPE_Q5_K || t == GGML_TYPE_Q6_K || t == GGML_TYPE_Q8_0; }
+static bool is_quant(int t) { return t == GGML_TYPE_Q4_K || t == GGML_TYPE_Q5_K || t == GGML_TYPE_Q6_K || t == GGML_TYPE_Q8_0 || is_l32_type(t); }
+// what the kernels over those formats assume of a matrix beyond contiguous rows: every block starts at the format's own alignment (2 bytes; 4 for the offset
+// formats, whose blocks are 20 / 24 bytes) — base address (null while the loader probes a type with a plain tensor: any real allocation is aligned), row and
+// matrix strides.  Their weights live in ordinary device buffers only: the split (-sm row) and row-parallel buffer types keep refusing them.
+static bool l32_layout_ok(const ggml_tensor * a) {
+    const size_t al = (a->type == GGML_TYPE_Q4_1 || a->type == GGML_TYPE_Q5_1) ? 4 : 2;
+    if ((((uintptr_t) a->data) % al) || (a->nb[1] % al) || (a->nb[2] % al) || (a->nb[3] % al)) return false;
+    return !buffer_is_rowpar(a->view_src ? a->view_src->buffer : a->buffer) && !buffer_is_split(a->buffer);
+}
 // batches at least this wide run on the matrix cores.  The option's default (3) is per weight type since round 6: Q4_K / Q6_K matrices take the weight-streaming
 // kernel from TWO columns on (a 2-sequence step of Llama-3-8B Q4_K_M: 2.89-3.03 -> 2.78 ms — the multi-column mat-vec path has none of the batch path's fusions,
 // 17 launches a layer), Q5_K stays at 3 (its skinny unit is slower: Qwen2-7B Q5_K_M 3.13 -> 3.79 ms with 2; profiles/r06_np2_min_cols.txt)
@@ -26,7 +34,11 @@ static inline int mmq_min_cols_for(const backend_ctx * c, int wtype) {
     if (c->opt.mmq_min_cols != 3) return c->opt.mmq_min_cols;
     return (wtype == GGML_TYPE_Q4_K || (wtype == GGML_TYPE_Q6_K && !c->mm_q5_major)) ? 2 : 3;
 }
-static int act_kind(int wtype) { return wtype == GGML_TYPE_Q8_0 ? GGML_TYPE_Q8_0 : GGML_TYPE_Q8_K; }
+// the reference's vec_dot_type: Q8_0 blocks for Q8_0 / Q4_0 / Q5_0 / IQ4_NL weights (one quantised row serves them all), Q8_1 for Q4_1 / Q5_1, Q8_K for the K-quants
+static int act_kind(int wtype) {
+    if (wtype == GGML_TYPE_Q4_1 || wtype == GGML_TYPE_Q5_1) return GGML_TYPE_Q8_1;
+    return (wtype == GGML_TYPE_Q8_0 || is_l32_type(wtype)) ? GGML_TYPE_Q8_0 : GGML_TYPE_Q8_K;
+}
 static bool is_f32_contig(const ggml_tensor * t) { return t->type == GGML_TYPE_F32 && ggml_abi_is_contiguous(t); }
 static bool rows_contig(const ggml_tensor * t) { return t->nb[0] == ggml_abi_type_size(t->type); }
 static bool same_shape(const ggml_tensor * a, const ggml_tensor * b) {
@@ -37,18 +49,18 @@ static bool same_shape(const ggml_tensor * a, const ggml_tensor * b) {
 // ------------------------------------------------------------------------------------------------ supports_op
 // MUL_MAT whose src0 is a KV-cache view kept in a block format or bf16 (K.q of the non-flash path with -ctk q8_0 / q4_0 / ...: llama.cpp asks flash
 // attention only of a quantised V): the view is expanded to f16 (kv_types.hip) and the f16 product runs on the image.  Weight matrices of the
-// mat-vec formats (2-D Q8_0 ...) keep their own kernels.
+// mat-vec formats (2-D Q8_0, Q4_0, Q4_1, Q5_0, Q5_1, IQ4_NL ...) keep their own kernels: this is asked first, and says no to them.
 static bool mm_cache_image_ok(const ggml_tensor * op) {
     const ggml_tensor * a = op->src[0];
     const ggml_tensor * b = op->src[1];
     if (!a || !b || b->type != GGML_TYPE_F32 || op->type != GGML_TYPE_F32 || !ggml_abi_is_contiguous(op)) return false;
     if (!(kv_type_is_block(a->type) || a->type == GGML_TYPE_BF16 || a->type == GGML_TYPE_Q8_0)) return false;
     // a VIEW into a cache (or a batch of matrices), never a plain 2-D weight: llama.cpp's loader probes every weight type with a plain tensor, and a model stored
-    // in q4_0 / q5_1 / bf16 ... must get the same answer there as at graph time — its mat-muls stay where they were (the CPU backend), they do not take an
-    // image of a whole weight matrix per step
+    // in q4_0 / q5_1 / bf16 ... must get the same answer there as at graph time — a q4_0 ... iq4_nl matrix goes to the quantised mat-vec / mat-mul kernels
+    // (supports_op below), a bf16 one stays on the CPU backend; neither takes an image of a whole weight matrix per step
     if (a->view_src == nullptr && a->ne[2] == 1) return false;
-    // ... nor a view of one: a 2-D view of a Q8_0 weight keeps the quantised mat-vec / mat-mul kernels (the integer-dot arithmetic of the reference), and
-    // weights in the other block formats stay where they were
+    // ... nor a view of one: a 2-D view of a weight in Q8_0 or a 4- / 5-bit block format keeps the quantised mat-vec / mat-mul kernels (the integer-dot
+    // arithmetic of the reference)
     const ggml_backend_buffer_t root = a->view_src && a->view_src->buffer ? a->view_src->buffer : a->buffer;
     if (root && root->usage == GGML_BACKEND_BUFFER_USAGE_WEIGHTS) return false;
     if (a->nb[0] != ggml_abi_type_size(a->type) || (a->ne[0] % 32) != 0 || (a->nb[1] % 2) || (a->nb[2] % 2) || a->ne[3] != 1 || b->ne[3] != 1 || b->nb[0] != 4) return false;
@@ -99,6 +111,7 @@ static bool mm_id_ok(const ggml_tensor * op) {
     const ggml_tensor * ids = op->src[2];
     if (!a || !b || !ids || b->type != GGML_TYPE_F32 || ids->type != GGML_TYPE_I32 || op->type != GGML_TYPE_F32 || !ggml_abi_is_contiguous(op)) return false;
     if (!(is_quant(a->type) || a->type == GGML_TYPE_F16 || a->type == GGML_TYPE_F32) || !rows_contig(a) || a->ne[3] != 1 || a->ne[0] % ggml_abi_blck_size(a->type) != 0) return false;
+    if (is_l32_type(a->type) && !l32_layout_ok(a)) return false;
     if (buffer_is_rowpar(a->view_src ? a->view_src->buffer : a->buffer)) return false;  // (row-parallel weights hold a slice of every row: MUL_MAT only)
     if (b->ne[0] != a->ne[0] || b->nb[0] != 4 || b->ne[3] != 1 || (b->nb[1] % 4) || (b->nb[2] % 4)) return false;
     if (ids->nb[0] != 4 || (ids->nb[1] % 4) || ids->ne[2] != 1 || ids->ne[3] != 1 || ids->ne[1] != b->ne[2] || ids->ne[0] < 1 || ids->ne[1] < 1) return false;
@@ -127,6 +140,7 @@ bool supports_op(const ggml_tensor * op) {
             if (buffer_is_split(a->buffer)) return split_mul_mat_supported(op);  // -sm row weights: every device computes its rows (split.cpp)
             if (mm_cache_image_ok(op)) return true;
             if (is_quant(a->type)) {
+                if (is_l32_type(a->type) && !l32_layout_ok(a)) return false;
                 return a->ne[2] == 1 && a->ne[3] == 1 && rows_contig(a) && b->nb[0] == 4 && a->ne[0] % ggml_abi_blck_size(a->type) == 0;
             }
             if (a->type == GGML_TYPE_F16 || a->type == GGML_TYPE_F32) return true;
@@ -166,6 +180,7 @@ bool supports_op(const ggml_tensor * op) {
             return (st == GGML_TYPE_F32 || st == GGML_TYPE_F16) && (dt == GGML_TYPE_F32 || dt == GGML_TYPE_F16);
         }
         case GGML_OP_GET_ROWS:
+            if (is_l32_type(a->type) && !l32_layout_ok(a)) return false;  // (token_embd in q4_0 ...: the block alignment and buffer types of the MUL_MAT arm)
             return b->type == GGML_TYPE_I32 && op->type == GGML_TYPE_F32 && rows_contig(a) && op->nb[0] == 4 &&
                    (is_quant(a->type) || a->type == GGML_TYPE_F16 || a->type == GGML_TYPE_F32);
         case GGML_OP_SET_ROWS:
@@ -437,7 +452,7 @@ static bool single_use(const exec_state & st, const ggml_tensor * t) { return us
 // already hold exactly this tensor (Q/K/V and gate/up share their input)
 static const void * quantized_src1(exec_state & st, const ggml_tensor * b, int wtype) {  // (wtype MI_ACT_Q80_PANEL: Q8_0 blocks in the panel order of the 9 .. 32-column kernel)
     backend_ctx * c = st.c;
-    const int kind = wtype == MI_ACT_Q80_PANEL ? MI_ACT_Q80_PANEL : act_kind(wtype);
+    const int kind = (wtype == MI_ACT_Q80_PANEL || wtype == MI_ACT_Q81_PANEL) ? wtype : act_kind(wtype);
     void * dst = (char *) c->ws + st.act_off;
     if (c->q8_src == b->data && c->q8_kind == kind && c->q8_bytes == ggml_abi_nbytes(b)) return dst;
     {
@@ -458,6 +473,11 @@ static const char * type_tag(int t) {
         case GGML_TYPE_Q5_K: return "q5_K";
         case GGML_TYPE_Q6_K: return "q6_K";
         case GGML_TYPE_Q8_0: return "q8_0";
+        case GGML_TYPE_Q4_0: return "q4_0";
+        case GGML_TYPE_Q4_1: return "q4_1";
+        case GGML_TYPE_Q5_0: return "q5_0";
+        case GGML_TYPE_Q5_1: return "q5_1";
+        case GGML_TYPE_IQ4_NL: return "iq4_nl";
         default: return "f";
     }
 }
@@ -538,6 +558,20 @@ static bool run_mul_mat_q(exec_state & st, const ggml_tensor * w, const ggml_ten
         timed_scope ts(c, cls, wbytes, true);
         launch_mmvq(c->stream, a, 1);
         c->st.kernel_launches++;
+        return true;
+    }
+    // Q4_0 .. IQ4_NL, 9 columns and more: the integer matrix cores (mmq_q80.hip with the format's staging step), never passes of the mat-vec kernel
+    const int l32_form = (is_l32_type(w->type) && !w2 && !add2) ? mmq_l32_form(w->type, K, N, M) : 0;
+    if (l32_form) {
+        const bool one = act_kind(w->type) == GGML_TYPE_Q8_1;
+        // (kinds as wtype: quantized_src1 maps a weight type through act_kind and takes a panel kind as it is)
+        const void * act = quantized_src1(st, b, l32_form == 1 ? (one ? MI_ACT_Q81_PANEL : MI_ACT_Q80_PANEL) : w->type);
+        timed_scope ts(c, (std::string("mmq_") + type_tag(w->type) + (l32_form == 1 ? "_skinny" : "")).c_str(), wbytes);
+        const int64_t arows = add ? add->ne[1] * add->ne[2] * add->ne[3] : 0;
+        launch_mmq_l32(c->stream, w->type, l32_form, (const uint8_t *) w->data, (int64_t) w->nb[1], (int) K, (int) N, (int) M, act, (float *) dst->data, (int64_t) (dst->nb[1] / 4),
+                       add ? (const float *) add->data : nullptr, (!add || arows == 1) ? 0 : (int64_t) (add->nb[1] / 4));
+        c->st.kernel_launches += l32_form == 1 ? (M + 31) / 32 : 1;
+        c->st.skinny_launches += l32_form == 1;
         return true;
     }
     const bool q80_skinny = w->type == GGML_TYPE_Q8_0 && !w2 && !add2 && mmq_q80_skinny_supported(w->type, K, N, M);
@@ -1853,7 +1887,8 @@ static int run_node(exec_state & st, int i) {
                 if (used != 0) return used;
             }
             if (fuse && !rowpar && ((M >= mmq_min_cols_for(c, a->type) && c->opt.mmq_i8 && mmq_i8_supported(a->type, a->ne[0], a->ne[1], M)) ||
-                                    (M >= c->opt.q80_min_cols && mmq_q80_supported(a->type, a->ne[0], a->ne[1], M)) || mmq_q80_skinny_supported(a->type, a->ne[0], a->ne[1], M))) {
+                                    (M >= c->opt.q80_min_cols && mmq_q80_supported(a->type, a->ne[0], a->ne[1], M)) || mmq_q80_skinny_supported(a->type, a->ne[0], a->ne[1], M) ||
+                                    mmq_l32_form(a->type, a->ne[0], a->ne[1], M) != 0)) {
                 // batches: MUL_MAT -> ADD (bias row or residual) rides in the GEMM's store
                 ggml_tensor * a1 = next(1);
                 const ggml_tensor * o1 = (a1 && single_use(st, n)) ? add_partner(a1, n) : nullptr;

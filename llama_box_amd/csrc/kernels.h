@@ -24,12 +24,15 @@ inline tdesc TD(const ggml_tensor * t) {
 
 // ---- activation quantisation (quantize.hip)
 // src: f32 rows of K elements (dim0 contiguous), any strides on dims 1..3; rows are enumerated i1 fastest.
-// kind: GGML_TYPE_Q8_K -> q8k_dev[rows][K/256]; GGML_TYPE_Q8_0 -> q80_dev[rows][K/32]
+// kind: GGML_TYPE_Q8_K -> q8k_dev[rows][K/256]; GGML_TYPE_Q8_0 -> q80_dev[rows][K/32]; GGML_TYPE_Q8_1 -> q81_dev[rows][K/32] (Q4_1 / Q5_1 weights);
+// MI_ACT_Q81_PANEL -> Q8_1 blocks in panel order (below)
 size_t quantized_act_bytes(int kind, int64_t K, int64_t rows);
 void launch_quantize_act(hipStream_t s, int kind, const tdesc & src, void * dst);
 // Q8_0 activations of up to 32 columns in PANEL order (mmq_q80.hip: k_mmq_q80_skinny): per block of 32 values [K half][column 0 .. 31][16 quants] + [column] f32 scales, 1152 B
 #define MI_ACT_Q80_PANEL 1008
 void launch_quantize_q80_panel(hipStream_t s, const tdesc & src, void * dst);
+// ... and Q8_1 activations in the same order for Q4_1 / Q5_1 weights: the tile's 32 f32 `s` (block_q8_1.s) follow its scales, 1280 B (launch_quantize_act)
+#define MI_ACT_Q81_PANEL 1009
 // producers fused with that quantisation (ops.hip; same arithmetic as the unfused kernels): RMS_NORM(x) * w, SwiGLU
 bool rms_norm_q80_panel_ok(const tdesc & src, const float * w);
 void launch_rms_norm_mul_q80_panel(hipStream_t s, const tdesc & src, float eps, const float * w, void * q80_panel);
@@ -231,6 +234,13 @@ bool mmq_q80_skinny_supported(int type, int64_t K, int64_t N, int64_t M);
 struct mmq80s_desc { const uint8_t * W; const uint8_t * W_panels; int64_t w_nb1; int N; float * dst; int64_t dst_stride; const float * add; int64_t add_stride; };
 void launch_mmq_q80_skinny_multi(hipStream_t s, int n, const mmq80s_desc * mats, int K, int M, const void * act_q80_panel);  // up to three matrices over the same activations
 void launch_mmq_q80_skinny(hipStream_t s, const uint8_t * W, const uint8_t * W_panels, int64_t w_nb1, int K, int N, int M, const void * act_q80_panel, float * dst, int64_t dst_stride, const float * add, int64_t add_stride);
+// the 4- and 5-bit formats of 32-value blocks (18 / 20 / 22 / 24 bytes): mat-vec decoders T_Q40 .. T_IQ4NL (mmvq_types.h), matrix-core forms in mmq_q80.hip
+inline bool is_l32_type(int t) { return t == GGML_TYPE_Q4_0 || t == GGML_TYPE_Q4_1 || t == GGML_TYPE_Q5_0 || t == GGML_TYPE_Q5_1 || t == GGML_TYPE_IQ4_NL; }
+// Q4_0 / Q4_1 / Q5_0 / Q5_1 / IQ4_NL weights, 9 columns and more, on the two kernels above with the staging step of the format (mmq_q80.hip).  mmq_l32_form:
+// 0 not served (K % 128 != 0, fewer than 9 columns: mat-vec passes), 1 the weight-streaming form — activations in panel order, MI_ACT_Q80_PANEL or (Q4_1 / Q5_1)
+// MI_ACT_Q81_PANEL, 2 the tiled form — activations as GGML_TYPE_Q8_0 / GGML_TYPE_Q8_1 rows
+int mmq_l32_form(int type, int64_t K, int64_t N, int64_t M);
+void launch_mmq_l32(hipStream_t s, int type, int form, const uint8_t * W, int64_t w_nb1, int K, int N, int M, const void * act, float * dst, int64_t dst_stride, const float * add, int64_t add_stride);
 void launch_mmq(hipStream_t s, int type, const uint8_t * W, int64_t w_nb1, int K, int N, int M, const void * act_q8k, float * dst, int64_t dst_stride, int ksplit, float * part);
 
 // ---- element-wise / normalisation / data movement (ops.hip)

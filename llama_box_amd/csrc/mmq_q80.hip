@@ -10,6 +10,7 @@
 // both operands in the XOR-swizzled [row][128 B] image of mmq_i8.hip plus the 4 block scales of every row / column.
 #include <algorithm>
 #include <cstdlib>
+#include <type_traits>
 
 #include "dev_util.h"
 #include "kernels.h"
@@ -34,13 +35,47 @@ struct mmq80_args {
 
 constexpr int Q80_T = 128 * 128;                // bytes of one operand tile
 constexpr int Q80_STAGE = 2 * Q80_T + 2 * 128 * 16;  // A | B | dw[128][4] | da[128][4]
+constexpr int Q80_STAGE1 = Q80_STAGE + 2 * 128 * 16; // ... | mw[128][4] | sa[128][4] (Q4_1 / Q5_1)
 
 __device__ __forceinline__ int sw_offq(const int row, const int chunk) { return row * 128 + ((chunk ^ ((row >> 1) & 7)) << 4); }
 
+// ---- weights in Q4_0 / Q4_1 / Q5_0 / Q5_1 / IQ4_NL (template parameter WT of both kernels; WT == GGML_TYPE_Q8_0 is the code as it was).  Every level of these
+// formats fits an int8 (Q4_0 -8 .. 7, Q5_0 -16 .. 15, IQ4_NL the table's -127 .. 113, Q4_1 0 .. 15, Q5_1 0 .. 31), so a decoded block IS a Q8_0 block with the
+// same d: only the step that fills the int8 operand differs, the MFMA and the f32 scale-accumulate are shared; the offset formats add m * s per block, s =
+// block_q8_1.s of the activation block (quantize.hip: k_quantize_q8_1).  These forms read the block layout (18 .. 24 bytes a block); there is no panel copy.
+template <int WT> struct l32_fmt {
+    static constexpr bool ONE = WT == GGML_TYPE_Q4_1 || WT == GGML_TYPE_Q5_1, FIVE = WT == GGML_TYPE_Q5_0 || WT == GGML_TYPE_Q5_1;
+    static constexpr int BYTES = WT == GGML_TYPE_Q8_0 ? 34 : 18 + (ONE ? 2 : 0) + (FIVE ? 4 : 0);
+    static constexpr int ACT = ONE ? 40 : 36;         // bytes of an activation block (q81_dev / q80_dev)
+    static constexpr int TILE = ONE ? 1280 : 1152;    // ... and of a panel-order tile (32 columns of one block)
+};
+// the 16 levels of half `half` (values 16 half .. 16 half + 15) of a block as signed bytes, from its 16 qs bytes and qh
+template <int WT> __device__ __forceinline__ void l32_half_levels(const uint32_t (&q)[4], const uint32_t qh, const int half, uint32_t (&t)[4]) {
+    typedef l32_fmt<WT> F;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        uint32_t v = (q[k] >> (4 * half)) & 0x0F0F0F0Fu;
+        if constexpr (F::FIVE) v |= ((((qh >> (16 * half + 4 * k)) & 0xFu) * 0x00204081u) & 0x01010101u) << 4;
+        if constexpr (WT == GGML_TYPE_IQ4_NL) {
+            constexpr uint32_t A0 = 0xBFAD9881u, A1 = 0xF6EADDCFu, B0 = 0x26190D01u, B1 = 0x71594535u;  // (mmvq_types.h: T_L32::levels)
+            const uint32_t sl = v & 0x07070707u, ml = ((v >> 3) & 0x01010101u) * 0xFFu;
+            v = (__builtin_amdgcn_perm(A1, A0, sl) & ~ml) | (__builtin_amdgcn_perm(B1, B0, sl) & ml);
+        } else if constexpr (!F::ONE) {
+            constexpr uint32_t Z = F::FIVE ? 0x10101010u : 0x08080808u;
+            v = ((v | 0x80808080u) - Z) ^ 0x80808080u;
+        }
+        t[k] = v;
+    }
+}
+
 // PANEL (round 6): the weights come from their panel copy (repack.hip: k_repack_q80_panels) and the activations in panel order (quantize.hip: k_quantize_q8_0<true>) —
 // a thread's block is two aligned 16-byte loads + its scale instead of eight 2-byte-aligned dwords + the scale, consecutive threads read consecutive bytes
-template <bool PANEL> __global__ void __launch_bounds__(512, 1) k_mmq_q80(const mmq80_args a) {
+template <bool PANEL, int WT = GGML_TYPE_Q8_0> __global__ void __launch_bounds__(512, 1) k_mmq_q80(const mmq80_args a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
+    typedef l32_fmt<WT> F;
+    constexpr bool L32 = WT != GGML_TYPE_Q8_0;
+    constexpr int STAGE = F::ONE ? Q80_STAGE1 : Q80_STAGE;
+    static_assert(!(PANEL && L32), "the panel copy is Q8_0's");
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int xcd = blockIdx.x & 7, qb = blockIdx.x >> 3;
     const int panel = (qb / a.m_tiles) * 8 + xcd, mt = qb % a.m_tiles;
@@ -51,8 +86,11 @@ template <bool PANEL> __global__ void __launch_bounds__(512, 1) k_mmq_q80(const 
 
     // staging roles: thread -> (row | column, block of the trip)
     const int srow = tid >> 2, sq = tid & 3;
-    const uint8_t * wblk = a.W + (size_t) min(n0 + srow, a.N - 1) * a.w_nb1 + (size_t) sq * 34;
+    const uint8_t * wblk = a.W + (size_t) min(n0 + srow, a.N - 1) * a.w_nb1 + (size_t) sq * F::BYTES;
     const q80_dev * yblk = a.act + (size_t) min(m0 + srow, a.M - 1) * nb32 + sq;
+    const char * yblk1 = (const char *) a.act + ((size_t) min(m0 + srow, a.M - 1) * nb32 + sq) * F::ACT;  // (Q4_1 / Q5_1: q81_dev rows)
+    uint32_t gqh = 0, ghdr = 0;  // (the 4- and 5-bit formats: qh and d | m << 16 of the block in flight)
+    float gbs = 0.0f;
     const int off0 = sw_offq(srow, 2 * sq), off1 = sw_offq(srow, 2 * sq + 1);
 
     uint32_t ga0, ga1, ga2, ga3, ga4, ga5, ga6, ga7, gb0, gb1, gb2, gb3, gb4, gb5, gb6, gb7;
@@ -74,6 +112,19 @@ template <bool PANEL> __global__ void __launch_bounds__(512, 1) k_mmq_q80(const 
             gbd = *(const float *) (yt + 1024 - (size_t) (ycol_c & 31) * 16 + (size_t) (ycol_c & 31) * 4);
             return;
         }
+        if constexpr (L32) {  // the raw block: header, qh, 16 qs bytes (stage() decodes them)
+            const uint8_t * p = wblk + (size_t) t * 4 * F::BYTES;
+            ghdr = F::ONE ? ld32_a2(p) : (uint32_t) ld16(p);
+            if constexpr (F::FIVE) gqh = ld32_a2(p + (F::ONE ? 4 : 2));
+            ga0 = ld32_a2(p + F::BYTES - 16); ga1 = ld32_a2(p + F::BYTES - 12); ga2 = ld32_a2(p + F::BYTES - 8); ga3 = ld32_a2(p + F::BYTES - 4);
+            gad = (uint16_t) (ghdr & 0xFFFFu);
+            const char * y = yblk1 + (size_t) t * 4 * F::ACT;
+            const uint32_t * yq = (const uint32_t *) y;
+            gb0 = yq[0]; gb1 = yq[1]; gb2 = yq[2]; gb3 = yq[3]; gb4 = yq[4]; gb5 = yq[5]; gb6 = yq[6]; gb7 = yq[7];
+            gbd = *(const float *) (y + 32);
+            if constexpr (F::ONE) gbs = *(const float *) (y + 36);
+            return;
+        }
         const uint8_t * p = wblk + (size_t) t * 4 * 34;  // Q8_0 blocks are 2-byte aligned: dword loads typed accordingly
         gad = ld16(p);
         ga0 = ld32_a2(p + 2); ga1 = ld32_a2(p + 6); ga2 = ld32_a2(p + 10); ga3 = ld32_a2(p + 14);
@@ -84,9 +135,22 @@ template <bool PANEL> __global__ void __launch_bounds__(512, 1) k_mmq_q80(const 
         gbd = y->d;
     };
     auto stage = [&](const int t) {
-        char * buf = smem + (t & 1) * Q80_STAGE;
+        char * buf = smem + (t & 1) * STAGE;
+        if constexpr (L32) {  // decode into the int8 image a Q8_0 block would have left
+            const uint32_t q[4] = {ga0, ga1, ga2, ga3};
+            uint32_t lo[4], hi[4];
+            l32_half_levels<WT>(q, gqh, 0, lo);
+            l32_half_levels<WT>(q, gqh, 1, hi);
+            *(uint4 *) (buf + off0) = make_uint4(lo[0], lo[1], lo[2], lo[3]);
+            *(uint4 *) (buf + off1) = make_uint4(hi[0], hi[1], hi[2], hi[3]);
+            if constexpr (F::ONE) {
+                ((float *) (buf + Q80_STAGE))[sq * 128 + srow] = h2f((uint16_t) (ghdr >> 16));
+                ((float *) (buf + Q80_STAGE + 128 * 16))[sq * 128 + srow] = gbs;
+            }
+        } else {
         *(uint4 *) (buf + off0) = make_uint4(ga0, ga1, ga2, ga3);
         *(uint4 *) (buf + off1) = make_uint4(ga4, ga5, ga6, ga7);
+        }
         *(uint4 *) (buf + Q80_T + off0) = make_uint4(gb0, gb1, gb2, gb3);
         *(uint4 *) (buf + Q80_T + off1) = make_uint4(gb4, gb5, gb6, gb7);
         ((float *) (buf + 2 * Q80_T))[sq * 128 + srow] = h2f(gad);              // scales are stored [block][row] so that the four
@@ -111,7 +175,7 @@ template <bool PANEL> __global__ void __launch_bounds__(512, 1) k_mmq_q80(const 
             stage(t + 1);
             if (t + 2 < trips) issue_loads(t + 2);
         }
-        const char * buf = smem + (t & 1) * Q80_STAGE;
+        const char * buf = smem + (t & 1) * STAGE;
         const float * dwt = (const float *) (buf + 2 * Q80_T);
         const float * dat = (const float *) (buf + 2 * Q80_T + 128 * 16);
 #pragma unroll
@@ -132,6 +196,17 @@ template <bool PANEL> __global__ void __launch_bounds__(512, 1) k_mmq_q80(const 
             for (int r = 0; r < 16; ++r) {
                 C0[r] += (float) s0[r] * (x[r] * y0);  // sumf += sumi * (d_w * d_x), as the CPU does
                 C1[r] += (float) s1[r] * (x[r] * y1);
+            }
+            if constexpr (F::ONE) {  // + m_w * s_x
+                const float * mwt = (const float *) (buf + Q80_STAGE);
+                const float * sat = (const float *) (buf + Q80_STAGE + 128 * 16);
+                const float z0 = sat[blk * 128 + mhalf * 64 + fr], z1 = sat[blk * 128 + mhalf * 64 + 32 + fr];
+#pragma unroll
+                for (int g4 = 0; g4 < 4; ++g4) {
+                    const float4 v = *(const float4 *) (mwt + blk * 128 + nslab * 32 + 8 * g4 + 4 * kg);
+                    C0[4 * g4] += v.x * z0; C0[4 * g4 + 1] += v.y * z0; C0[4 * g4 + 2] += v.z * z0; C0[4 * g4 + 3] += v.w * z0;
+                    C1[4 * g4] += v.x * z1; C1[4 * g4 + 1] += v.y * z1; C1[4 * g4 + 2] += v.z * z1; C1[4 * g4 + 3] += v.w * z1;
+                }
             }
         }
         __syncthreads();
@@ -166,7 +241,6 @@ bool mmq_q80_supported(int type, int64_t K, int64_t N, int64_t M) {
     (void) N;
     return type == GGML_TYPE_Q8_0 && (K % 128) == 0 && M >= 9;
 }
-
 void launch_mmq_q80(hipStream_t s, const uint8_t * W, const uint8_t * W_panels, int64_t w_nb1, int K, int N, int M, const void * act_q80, float * dst, int64_t dst_stride, const float * add,
                     int64_t add_stride) {  // W_panels != nullptr: the panel copy, and act_q80 holds the activations in panel order
     mmq80_args a;
@@ -222,8 +296,12 @@ typedef uint32_t __attribute__((ext_vector_type(4), aligned(2))) q80s_u32x4_a2;
 typedef uint32_t __attribute__((ext_vector_type(4), aligned(4))) q80s_u32x4_a4;
 
 constexpr int Q80S_WV = 8;
-template <bool WP> __global__ void __launch_bounds__(Q80S_WV * 64, 2) k_mmq_q80_skinny(const mmq80s_args a) {
+template <bool WP, int WT = GGML_TYPE_Q8_0> __global__ void __launch_bounds__(Q80S_WV * 64, 2) k_mmq_q80_skinny(const mmq80s_args a) {
     constexpr bool PF = true;
+    typedef l32_fmt<WT> F;
+    constexpr bool L32 = WT != GGML_TYPE_Q8_0;
+    static_assert(!(WP && L32), "the panel copy is Q8_0's");
+    __shared__ float mwl[F::ONE ? Q80S_WV : 1][4][32];  // (Q4_1 / Q5_1) ... and their m
     __shared__ float dwl[Q80S_WV][4][32];       // a chunk's row scales, per wave
     __shared__ float red[Q80S_WV][16][64];      // the waves' partial tiles
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -243,34 +321,47 @@ template <bool WP> __global__ void __launch_bounds__(Q80S_WV * 64, 2) k_mmq_q80_
     for (int r = 0; r < 16; ++r) zi[r] = 0;
 
     int4q fa[4], fb[4], nfa[4], nfb[4];
-    uint16_t dw[4], ndw[4];
+    typedef typename std::conditional<L32, uint32_t, uint16_t>::type hdr_t;  // (4- and 5-bit formats: d | m << 16)
+    hdr_t dw[4], ndw[4];
     float dy[4], ndy[4];
-    auto load_chunk = [&](const int c, int4q * A, int4q * B, uint16_t * dW, float * dY) {
+    uint32_t qh[L32 ? 4 : 1], nqh[L32 ? 4 : 1];  // (5-bit formats)
+    float sy[L32 ? 4 : 1], nsy[L32 ? 4 : 1];     // (offset formats: block_q8_1.s of the column)
+    auto load_chunk = [&](const int c, int4q * A, int4q * B, hdr_t * dW, float * dY, uint32_t * QH, float * SY) {
 #pragma unroll
         for (int b = 0; b < 4; ++b) {
             if constexpr (WP) {  // the chunk's tile of the panel copy: a wave-instruction reads 1 KB of consecutive bytes
                 const uint8_t * tile = wrow + (size_t) c * 4352;
                 A[b] = *(const int4q *) (tile + b * 1024 + kg * 512 + fr * 16);
                 dW[b] = *(const uint16_t *) (tile + 4096 + b * 64 + fr * 2);
+            } else if constexpr (L32) {  // the raw block (both halves of a row read the same 16 qs bytes: low / high nibbles); decoded at use
+                const uint8_t * blk = wrow + (size_t) (c * 4 + b) * F::BYTES;
+                dW[b] = F::ONE ? ld32_a2(blk) : (uint32_t) ld16(blk);
+                if constexpr (F::FIVE) QH[b] = ld32_a2(blk + (F::ONE ? 4 : 2));
+                A[b] = __builtin_bit_cast(int4q, *(const q80s_u32x4_a2 *) (blk + F::BYTES - 16));
             } else {
                 const uint8_t * blk = wrow + (size_t) (c * 4 + b) * 34;
                 dW[b] = ld16(blk);
                 A[b] = __builtin_bit_cast(int4q, *(const q80s_u32x4_a2 *) (blk + 2 + 16 * kg));
             }
-            const char * yt = a.act + (size_t) (c * 4 + b) * 1152;
+            const char * yt = a.act + (size_t) (c * 4 + b) * F::TILE;
             B[b] = *(const int4q *) (yt + kg * 512 + colc * 16);
             dY[b] = *(const float *) (yt + 1024 + colc * 4);
+            if constexpr (F::ONE) SY[b] = *(const float *) (yt + 1152 + colc * 4);
         }
     };
     int c = wave;
-    if (c < nchunk) load_chunk(c, fa, fb, dw, dy);
+    if (c < nchunk) load_chunk(c, fa, fb, dw, dy, qh, sy);
     for (; c < nchunk; c += Q80S_WV) {
         const int cn = c + Q80S_WV;
-        if constexpr (PF) { if (cn < nchunk) load_chunk(cn, nfa, nfb, ndw, ndy); }
+        if constexpr (PF) { if (cn < nchunk) load_chunk(cn, nfa, nfb, ndw, ndy, nqh, nsy); }
         // the block scales of the 32 rows: written by the row's first lane, read back as the 16 rows of this lane's accumulator registers
         if (kg == 0) {
 #pragma unroll
-            for (int b = 0; b < 4; ++b) dwl[wave][b][fr] = h2f(dw[b]);
+            for (int b = 0; b < 4; ++b) dwl[wave][b][fr] = h2f((uint16_t) (dw[b] & 0xFFFFu));
+            if constexpr (F::ONE) {
+#pragma unroll
+                for (int b = 0; b < 4; ++b) mwl[wave][b][fr] = h2f((uint16_t) ((uint32_t) dw[b] >> 16));
+            }
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
@@ -283,9 +374,23 @@ template <bool WP> __global__ void __launch_bounds__(Q80S_WV * 64, 2) k_mmq_q80_
                 const float4 v = *(const float4 *) &dwl[wave][b][8 * g4 + 4 * kg];
                 x[4 * g4] = v.x; x[4 * g4 + 1] = v.y; x[4 * g4 + 2] = v.z; x[4 * g4 + 3] = v.w;
             }
-            const int16q s = __builtin_amdgcn_mfma_i32_32x32x32_i8(fa[b], fb[b], zi, 0, 0, 0);
+            int4q fab = fa[b];
+            if constexpr (L32) {
+                const uint32_t q[4] = {(uint32_t) fa[b][0], (uint32_t) fa[b][1], (uint32_t) fa[b][2], (uint32_t) fa[b][3]};
+                uint32_t t[4];
+                l32_half_levels<WT>(q, qh[b], kg, t);
+                fab[0] = (int) t[0]; fab[1] = (int) t[1]; fab[2] = (int) t[2]; fab[3] = (int) t[3];
+            }
+            const int16q s = __builtin_amdgcn_mfma_i32_32x32x32_i8(fab, fb[b], zi, 0, 0, 0);
 #pragma unroll
             for (int r = 0; r < 16; ++r) C[r] += (float) s[r] * (x[r] * dy[b]);  // sumf += sumi * (d_w * d_x), as the CPU does
+            if constexpr (F::ONE) {  // + m_w * s_x
+#pragma unroll
+                for (int g4 = 0; g4 < 4; ++g4) {
+                    const float4 v = *(const float4 *) &mwl[wave][b][8 * g4 + 4 * kg];
+                    C[4 * g4] += v.x * sy[b]; C[4 * g4 + 1] += v.y * sy[b]; C[4 * g4 + 2] += v.z * sy[b]; C[4 * g4 + 3] += v.w * sy[b];
+                }
+            }
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();  // (the next chunk's scales overwrite the line)
@@ -293,8 +398,12 @@ template <bool WP> __global__ void __launch_bounds__(Q80S_WV * 64, 2) k_mmq_q80_
             if constexpr (PF) {
 #pragma unroll
                 for (int b = 0; b < 4; ++b) { fa[b] = nfa[b]; fb[b] = nfb[b]; dw[b] = ndw[b]; dy[b] = ndy[b]; }
+                if constexpr (L32) {
+#pragma unroll
+                    for (int b = 0; b < 4; ++b) { qh[b] = nqh[b]; sy[b] = nsy[b]; }
+                }
             } else {
-                load_chunk(cn, fa, fb, dw, dy);
+                load_chunk(cn, fa, fb, dw, dy, qh, sy);
             }
         }
     }
@@ -347,6 +456,63 @@ void launch_mmq_q80_skinny(hipStream_t s, const uint8_t * W, const uint8_t * W_p
     const mmq80s_desc d{W, W_panels, w_nb1, N, dst, dst_stride, add, add_stride};
     launch_mmq_q80_skinny_multi(s, 1, &d, K, M, act_q80);
 }
+
+// Q4_0 / Q4_1 / Q5_0 / Q5_1 / IQ4_NL weights on the same two kernels, their staging step instantiated for the format (block layout only): 9 .. 128 columns
+// the weight-streaming form (activations in panel order: MI_ACT_Q80_PANEL, or MI_ACT_Q81_PANEL for the offset formats), wider batches the tiled form
+// (activations as q80_dev / q81_dev rows).  K % 128 != 0 falls back to mat-vec passes, as Q8_0 does.
+int mmq_l32_form(int type, int64_t K, int64_t N, int64_t M) {
+    if (!is_l32_type(type) || (K % 128) != 0 || N < 1 || M < 9) return 0;
+    return M <= 128 ? 1 : 2;
+}
+template <int WT> static void launch_mmq_l32_t(hipStream_t s, int form, const uint8_t * W, int64_t w_nb1, int K, int N, int M, const void * act, float * dst, int64_t dst_stride, const float * add,
+                                                int64_t add_stride) {
+    typedef l32_fmt<WT> F;
+    if (form == 1) {
+        mmq80s_args a;
+        const int pe = (N + 31) / 32;
+        for (int q = 0; q < 3; ++q) a.m[q] = {W, w_nb1, N, pe, dst, dst_stride, add, add_stride};
+        a.K = K;
+        for (int m0 = 0; m0 < M; m0 += 32) {
+            a.M = std::min(32, M - m0);
+            a.act = (const char *) act + (size_t) (m0 / 32) * (size_t) (K / 32) * F::TILE;
+            for (int q = 0; q < 3; ++q) {
+                a.m[q].dst = dst + (size_t) m0 * dst_stride;
+                a.m[q].add = add ? add + (size_t) m0 * add_stride : nullptr;
+            }
+            hipLaunchKernelGGL((k_mmq_q80_skinny<false, WT>), dim3((unsigned) pe), dim3(Q80S_WV * 64), 0, s, a);
+        }
+        return;
+    }
+    mmq80_args a;
+    a.W = W;
+    a.w_nb1 = w_nb1;
+    a.K = K;
+    a.N = N;
+    a.M = M;
+    a.act = (const q80_dev *) act;
+    a.dst = dst;
+    a.dst_stride = dst_stride;
+    a.n_panels = (N + 127) / 128;
+    a.m_tiles = (M + 127) / 128;
+    a.add = add;
+    a.add_stride = add_stride;
+    const size_t lds = 2 * (size_t) (F::ONE ? Q80_STAGE1 : Q80_STAGE);
+    static std::atomic<uint32_t> lds_raised{0};
+    (void) ensure_dyn_lds((const void *) k_mmq_q80<false, WT>, lds, lds_raised);
+    const unsigned grid = (unsigned) (((a.n_panels + 7) / 8) * 8 * a.m_tiles);
+    hipLaunchKernelGGL((k_mmq_q80<false, WT>), dim3(grid), dim3(512), lds, s, a);
+}
+void launch_mmq_l32(hipStream_t s, int type, int form, const uint8_t * W, int64_t w_nb1, int K, int N, int M, const void * act, float * dst, int64_t dst_stride, const float * add, int64_t add_stride) {
+    switch (type) {
+        case GGML_TYPE_Q4_0: launch_mmq_l32_t<GGML_TYPE_Q4_0>(s, form, W, w_nb1, K, N, M, act, dst, dst_stride, add, add_stride); break;
+        case GGML_TYPE_Q4_1: launch_mmq_l32_t<GGML_TYPE_Q4_1>(s, form, W, w_nb1, K, N, M, act, dst, dst_stride, add, add_stride); break;
+        case GGML_TYPE_Q5_0: launch_mmq_l32_t<GGML_TYPE_Q5_0>(s, form, W, w_nb1, K, N, M, act, dst, dst_stride, add, add_stride); break;
+        case GGML_TYPE_Q5_1: launch_mmq_l32_t<GGML_TYPE_Q5_1>(s, form, W, w_nb1, K, N, M, act, dst, dst_stride, add, add_stride); break;
+        case GGML_TYPE_IQ4_NL: launch_mmq_l32_t<GGML_TYPE_IQ4_NL>(s, form, W, w_nb1, K, N, M, act, dst, dst_stride, add, add_stride); break;
+        default: MI_ERR("launch_mmq_l32: unsupported weight type %d", type); abort();
+    }
+}
+
 
 MI_TU_TOUCH(mmq_q80)
 

@@ -517,7 +517,9 @@ template <typename T> static void launch_type(hipStream_t s, const mmvq_args & a
             return;
         }
     }
-    if (a0.x != nullptr || a0.fa_part != nullptr) {
+    if constexpr (mmvq_is_l32_t<T>::value) {  // Q4_0 .. IQ4_NL: no prologue forms (their activations arrive quantised: graph.cpp never asks)
+        if (a0.x != nullptr || a0.fa_part != nullptr) { MI_ERR("launch_mmvq: weight type %d has no activation prologue", a0.type); abort(); }
+    } else if (a0.x != nullptr || a0.fa_part != nullptr) {
         if ((a0.K % 256) != 0) {
             MI_ERR("launch_mmvq: the f32 prologue needs K %% 256 == 0 (K = %d)", a0.K);
             abort();
@@ -605,6 +607,11 @@ void launch_mmvq(hipStream_t s, const mmvq_args & a, int rows_per_wave) {
         case GGML_TYPE_Q5_K: launch_type<T_Q5K>(s, a, rows_per_wave); break;
         case GGML_TYPE_Q6_K: launch_type<T_Q6K>(s, a, rows_per_wave); break;
         case GGML_TYPE_Q8_0: launch_type<T_Q80>(s, a, rows_per_wave); break;
+        case GGML_TYPE_Q4_0: launch_type<T_Q40>(s, a, rows_per_wave); break;
+        case GGML_TYPE_Q4_1: launch_type<T_Q41>(s, a, rows_per_wave); break;
+        case GGML_TYPE_Q5_0: launch_type<T_Q50>(s, a, rows_per_wave); break;
+        case GGML_TYPE_Q5_1: launch_type<T_Q51>(s, a, rows_per_wave); break;
+        case GGML_TYPE_IQ4_NL: launch_type<T_IQ4NL>(s, a, rows_per_wave); break;
         default: MI_ERR("launch_mmvq: unsupported weight type %d", a.type); abort();
     }
 }

@@ -2,6 +2,8 @@
 // Each type T provides:  raw (the registers one lane holds for one (super-block, chunk) "pair"),  load(row, p),
 // dot<NC>(raw, p, activations, nblk, acc)  and the same pair expressed over a flat dword buffer (loadu/dotu, DW dwords).
 #pragma once
+#include <type_traits>
+
 #include "dev_util.h"
 #include "kernels.h"
 
@@ -249,7 +251,83 @@ struct T_Q80 {
     }
 };
 
-
+// ------------------------------------------------------------------------------------------------ Q4_0, Q4_1, Q5_0, Q5_1, IQ4_NL
+// Blocks of 32 values in 18 / 20 / 22 / 24 bytes: {d [, m] [, qh[4]], qs[16]}; value j < 16 is the LOW nibble of qs[j], value j + 16 its HIGH nibble, the
+// fifth bit of value j is bit j of qh.  One lane owns ONE block, as T_Q80 does: the 16 bytes of qs are one load typed with the format's 2-byte alignment
+// (gfx950 serves an unaligned global_load_dwordx4, as for Q6_K), the header (d, or d | m as one dword — the offset formats' blocks are 4-byte aligned) and qh
+// one load each.  A wave's 64 blocks are 1152 .. 1536 consecutive bytes = 9 .. 12 whole lines of a row, and every line is requested by the qs instruction
+// once: two or three wave-instructions per 64 blocks against T_Q80's nine.  (More blocks per lane would shorten K = 4096 — 128 blocks — to one trip of half
+// a wave; fewer would split the 16 qs bytes whose low and high nibbles belong to activation halves 16 values apart.)
+// The levels become signed bytes (n - 8, n - 16 subtracted per byte; the non-linear table through two byte permutes) and meet the int8 activations in
+// v_dot4_i32_i8; one f32 term per block follows in the expression of the reference's ggml_vec_dot_*: Q4_0 (sumi * d) * dy, Q5_0 / IQ4_NL (d * dy) * sumi,
+// Q4_1 / Q5_1 (d * dy) * sumi + m * s with s = block_q8_1.s of the activation block.
+template <int TYPE> struct T_L32 {
+    static constexpr bool ONE = TYPE == GGML_TYPE_Q4_1 || TYPE == GGML_TYPE_Q5_1, FIVE = TYPE == GGML_TYPE_Q5_0 || TYPE == GGML_TYPE_Q5_1;
+    typedef typename std::conditional<ONE, q81_dev, q80_dev>::type act;
+    static constexpr int BLK = 32, BYTES = 18 + (ONE ? 2 : 0) + (FIVE ? 4 : 0), PPB = 1;
+    struct raw { u128_a2 q; uint32_t h, qh; };  // h = d | m << 16
+    static constexpr int DW = FIVE ? 6 : 5;
+    static __device__ __forceinline__ raw load(const uint8_t * __restrict__ row, int p, int = 0) {
+        const uint8_t * blk = row + (size_t) p * BYTES;
+        raw r;
+        r.h = ONE ? ld32_a2(blk) : (uint32_t) ld16(blk);
+        r.qh = FIVE ? ld32_a2(blk + (ONE ? 4 : 2)) : 0u;
+        r.q = ld_stream((const u128_a2 *) (blk + BYTES - 16));
+        return r;
+    }
+    // the block's 32 levels as signed bytes: lo[k] = values 4k .. 4k + 3, hi[k] = values 16 + 4k .. 16 + 4k + 3
+    static __device__ __forceinline__ void levels(const raw & r, uint32_t (&lo)[4], uint32_t (&hi)[4]) {
+        const uint32_t q[4] = {r.q.x, r.q.y, r.q.z, r.q.w};
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            uint32_t l = q[k] & 0x0F0F0F0Fu, h = (q[k] >> 4) & 0x0F0F0F0Fu;
+            if constexpr (FIVE) {  // bit i of a nibble of qh to bit 4 of byte i (x * (1 + 2^7 + 2^14 + 2^21) puts bit i at 8 i)
+                l |= ((((r.qh >> (4 * k)) & 0xFu) * 0x00204081u) & 0x01010101u) << 4;
+                h |= ((((r.qh >> (16 + 4 * k)) & 0xFu) * 0x00204081u) & 0x01010101u) << 4;
+            }
+            if constexpr (TYPE == GGML_TYPE_IQ4_NL) {
+                // {-127, -104, -83, -65 | -49, -35, -22, -10 || 1, 13, 25, 38 | 53, 69, 89, 113}: bit 3 of a nibble picks the 8-entry table
+                constexpr uint32_t A0 = 0xBFAD9881u, A1 = 0xF6EADDCFu, B0 = 0x26190D01u, B1 = 0x71594535u;
+                const uint32_t sl = l & 0x07070707u, sh = h & 0x07070707u;
+                const uint32_t ml = ((l >> 3) & 0x01010101u) * 0xFFu, mh = ((h >> 3) & 0x01010101u) * 0xFFu;
+                l = (__builtin_amdgcn_perm(A1, A0, sl) & ~ml) | (__builtin_amdgcn_perm(B1, B0, sl) & ml);
+                h = (__builtin_amdgcn_perm(A1, A0, sh) & ~mh) | (__builtin_amdgcn_perm(B1, B0, sh) & mh);
+            } else if constexpr (!ONE) {  // n - Z per byte without a borrow between bytes: ((n | 0x80) - Z) ^ 0x80
+                constexpr uint32_t Z = FIVE ? 0x10101010u : 0x08080808u;
+                l = ((l | 0x80808080u) - Z) ^ 0x80808080u;
+                h = ((h | 0x80808080u) - Z) ^ 0x80808080u;
+            }
+            lo[k] = l;
+            hi[k] = h;
+        }
+    }
+    template <int NC> static __device__ __forceinline__ void dot(const raw & r, int p, const act * __restrict__ y, int nblk, float * acc) {
+        const float d = h2f((uint16_t) (r.h & 0xFFFFu));
+        uint32_t lo[4], hi[4];
+        levels(r, lo, hi);
+#pragma unroll
+        for (int col = 0; col < NC; ++col) {
+            const act * yb = y + (size_t) col * nblk + p;
+            const int * yq = (const int *) yb->qs;
+            int s = 0;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                s = dot4((int) lo[k], yq[k], s);
+                s = dot4((int) hi[k], yq[4 + k], s);
+            }
+            if constexpr (ONE) acc[col] += (d * yb->d) * (float) s + h2f((uint16_t) (r.h >> 16)) * yb->s;
+            else if constexpr (TYPE == GGML_TYPE_Q4_0) acc[col] += ((float) s * d) * yb->d;
+            else acc[col] += (d * yb->d) * (float) s;
+        }
+    }
+};
+typedef T_L32<GGML_TYPE_Q4_0> T_Q40;
+typedef T_L32<GGML_TYPE_Q4_1> T_Q41;
+typedef T_L32<GGML_TYPE_Q5_0> T_Q50;
+typedef T_L32<GGML_TYPE_Q5_1> T_Q51;
+typedef T_L32<GGML_TYPE_IQ4_NL> T_IQ4NL;
+template <typename T> struct mmvq_is_l32_t : std::false_type {};
+template <int TYPE> struct mmvq_is_l32_t<T_L32<TYPE>> : std::true_type {};
 
 // ------------------------------------------------------------------------------------------------ the plane layouts of the decode copy (see the top of this file)
 // (a row whose super-block count is not a multiple of 8 — Qwen2-7B: 14 and 74 — ends in a SHORT group of nb = nblk % 8 super-blocks with the same plane order,

@@ -8,6 +8,7 @@
 
 #include "dev_util.h"
 #include "kernels.h"
+#include "kv_dequant.h"
 
 namespace mi355x {
 
@@ -367,6 +368,17 @@ __device__ __forceinline__ float dequant_elem(const int type, const uint8_t * __
             const int q = (int) (int8_t) (nib | (((qh[l] >> (2 * k)) & 3) << 4)) - 32;
             const float d = h2f(ld16(b + 208));
             return d * (float) sc[(l >> 4) + 2 * k] * (float) q;
+        }
+        case GGML_TYPE_Q4_0: case GGML_TYPE_Q4_1: case GGML_TYPE_Q5_0: case GGML_TYPE_Q5_1: case GGML_TYPE_IQ4_NL: {
+            // dequantize_row_* through the octet helpers the KV cache in these formats is read with (kv_dequant.h): level * d (+ m), one rounding an operation
+            const char * b = (const char *) row + (i >> 5) * kv_block_bytes_any(type);
+            const int o = (int) (i & 31) >> 3, j = (int) (i & 7);
+            float y[8];
+            kv_octet_f32(type, kv_load_octet_raw(type, b, o), o, y);
+            float v = y[0];
+#pragma unroll
+            for (int k = 1; k < 8; ++k) v = j == k ? y[k] : v;
+            return v;
         }
         default: return 0.0f;
     }

@@ -70,6 +70,66 @@ __global__ void __launch_bounds__(64) k_quantize_q8_0(const char * __restrict__ 
     }
 }
 
+// Q8_1 activations (Q4_1 / Q5_1 weights): the Q8_0 block of the kernel above plus block_q8_1.s = f16(sum(qs) * d) with the UNROUNDED d = amax / 127
+// (quantize_row_q8_1_ref).  PANEL: the panel order of the 9+-column matrix-core kernels with the 32 columns' s behind their scales, 1280 B per block
+template <bool PANEL>
+__global__ void __launch_bounds__(64) k_quantize_q8_1(const char * __restrict__ src, int64_t ne1, int64_t ne2, int64_t nb1, int64_t nb2,
+                                                      int64_t nb3, int K, int chunks_per_row, q81_dev * __restrict__ dst) {
+    const int64_t gid = blockIdx.x;
+    const int64_t row = gid / chunks_per_row;
+    const int ic = (int) (gid - row * chunks_per_row);
+    const int64_t i1 = row % ne1, i2 = (row / ne1) % ne2, i3 = row / (ne1 * ne2);
+    const float * xrow = (const float *) (src + i1 * nb1 + i2 * nb2 + i3 * nb3);
+    const int lane = threadIdx.x;
+    const int e0 = ic * 256 + lane * 4;
+    const bool live = e0 < K;  // K is a multiple of 32, so a block is either entirely live or entirely dead
+    float v[4] = {0, 0, 0, 0};
+    if (live) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) v[k] = xrow[e0 + k];
+    }
+    float amax = fmaxf(fmaxf(fabsf(v[0]), fabsf(v[1])), fmaxf(fabsf(v[2]), fabsf(v[3])));
+    amax = fmaxf(amax, __shfl_xor(amax, 1, 64));
+    amax = fmaxf(amax, __shfl_xor(amax, 2, 64));
+    amax = fmaxf(amax, __shfl_xor(amax, 4, 64));
+    const float d = amax / 127.0f;
+    const float id = d != 0.0f ? 1.0f / d : 0.0f;
+    uint32_t packed = 0;
+    int sum = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int r = (int) roundf(v[k] * id);
+        packed |= (uint32_t) (r & 0xFF) << (8 * k);
+        sum += (int) (int8_t) r;
+    }
+    sum += __shfl_xor(sum, 1, 64);
+    sum += __shfl_xor(sum, 2, 64);
+    sum += __shfl_xor(sum, 4, 64);
+    if (!live) return;
+    // sum * d is rounded to f32 FIRST and to f16 after, as the reference's two statements do.  Left to itself the compiler merges the multiply and the
+    // conversion into one v_fma_mixlo_f16 — a single rounding, one f16 ulp away from block_q8_1.s whenever the f32 product rounds onto an f16 tie
+    // (about one block in 2^13) — so the f32 product is made opaque to it
+    float prod = (float) sum * d;
+    asm volatile("" : "+v"(prod));
+    const float sv = h2f(f2h(prod));
+    if constexpr (PANEL) {
+        char * tile = (char *) dst + ((size_t) (row >> 5) * (size_t) (K / 32) + (size_t) (e0 >> 5)) * 1280;
+        const int w8 = lane & 7, cr = (int) (row & 31);
+        *(uint32_t *) (tile + (w8 >> 2) * 512 + cr * 16 + (w8 & 3) * 4) = packed;
+        if (w8 == 0) {
+            *(float *) (tile + 1024 + cr * 4) = h2f(f2h(d));
+            *(float *) (tile + 1152 + cr * 4) = sv;
+        }
+    } else {
+        q81_dev * y = dst + row * (int64_t) (K / 32) + (e0 >> 5);
+        ((uint32_t *) y->qs)[lane & 7] = packed;
+        if ((lane & 7) == 0) {
+            y->d = h2f(f2h(d));
+            y->s = sv;
+        }
+    }
+}
+
 // ---- producers fused with the quantisation (batches: the f32 intermediate is never written).  Same f32 arithmetic as the
 // stand-alone kernels (ops.hip k_rms_norm + k_binary MUL, k_swiglu), so the Q8_K blocks are the ones the unfused path builds.
 // RMS_NORM(x) * w -> Q8_K: one 16-wave workgroup per row, wave w owns blocks w, w+16, w+32, w+48 (K <= 16384)
@@ -165,6 +225,7 @@ void launch_swiglu_quantize(hipStream_t s, const tdesc & a, const tdesc * b, int
 
 size_t quantized_act_bytes(int kind, int64_t K, int64_t rows) {
     if (kind == GGML_TYPE_Q8_K) return (size_t) rows * (size_t) (K / 256) * sizeof(q8k_dev);
+    if (kind == GGML_TYPE_Q8_1) return (size_t) rows * (size_t) (K / 32) * sizeof(q81_dev);  // (= 1280 B per 32 columns and block: the panel order as well)
     return (size_t) rows * (size_t) (K / 32) * sizeof(q80_dev);
 }
 
@@ -174,6 +235,10 @@ void launch_quantize_act(hipStream_t s, int kind, const tdesc & src, void * dst)
     if (kind == GGML_TYPE_Q8_K) {
         const int nb = (int) (K / 256);
         hipLaunchKernelGGL(k_quantize_q8_K, dim3((unsigned) (rows * nb)), dim3(64), 0, s, src.data, src.ne[1], src.ne[2], src.nb[1], src.nb[2], src.nb[3], nb, (q8k_dev *) dst);
+    } else if (kind == GGML_TYPE_Q8_1 || kind == MI_ACT_Q81_PANEL) {
+        const int chunks = (int) ((K + 255) / 256);
+        if (kind == MI_ACT_Q81_PANEL) hipLaunchKernelGGL(k_quantize_q8_1<true>, dim3((unsigned) (rows * chunks)), dim3(64), 0, s, src.data, src.ne[1], src.ne[2], src.nb[1], src.nb[2], src.nb[3], (int) K, chunks, (q81_dev *) dst);
+        else hipLaunchKernelGGL(k_quantize_q8_1<false>, dim3((unsigned) (rows * chunks)), dim3(64), 0, s, src.data, src.ne[1], src.ne[2], src.nb[1], src.nb[2], src.nb[3], (int) K, chunks, (q81_dev *) dst);
     } else {
         const int chunks = (int) ((K + 255) / 256);
         hipLaunchKernelGGL(k_quantize_q8_0<false>, dim3((unsigned) (rows * chunks)), dim3(64), 0, s, src.data, src.ne[1], src.ne[2], src.nb[1], src.nb[2], src.nb[3], (int) K, chunks, (q80_dev *) dst);

@@ -117,6 +117,18 @@ static void synth_block(ggml_type type, uint64_t key, int64_t K, float wscale, u
             }
             b->d = f32_to_f16(scale * rk / (70.0f * 18.5f));
         } break;
+        case GGML_TYPE_Q4_0: case GGML_TYPE_Q4_1: case GGML_TYPE_Q5_0: case GGML_TYPE_Q5_1: case GGML_TYPE_IQ4_NL: {
+            // {d [, m] [, qh[4]], qs[16]} (include/ggml_abi.h): uniform levels; the offset formats' m centres them (m = -mean level * d)
+            const bool one = type == GGML_TYPE_Q4_1 || type == GGML_TYPE_Q5_1, five = type == GGML_TYPE_Q5_0 || type == GGML_TYPE_Q5_1;
+            const float qmean = five ? 15.5f : 7.5f, qstd = type == GGML_TYPE_IQ4_NL ? 70.0f : (five ? 9.2f : 4.6f);
+            const float d = scale * rk / qstd;
+            const uint16_t hd = f32_to_f16(d), hm = f32_to_f16(-d * qmean);
+            uint8_t * p = out;
+            memcpy(p, &hd, 2);
+            p += 2;
+            if (one) { memcpy(p, &hm, 2); p += 2; }
+            fill(p, five ? 20 : 16);
+        } break;
         default: LLM_ASSERT(!"synth_block: unsupported type");
     }
 }
@@ -182,6 +194,24 @@ static void block_values(ggml_type type, const uint8_t * p, float * y) {
                     y[128 * n + l + 64] = d * (float) sc[is + 4] * (float) q3;
                     y[128 * n + l + 96] = d * (float) sc[is + 6] * (float) q4;
                 }
+            }
+        } break;
+        case GGML_TYPE_Q4_0: case GGML_TYPE_Q4_1: case GGML_TYPE_Q5_0: case GGML_TYPE_Q5_1: case GGML_TYPE_IQ4_NL: {  // the 32 values of one block
+            static const int8_t iq4nl[16] = {-127, -104, -83, -65, -49, -35, -22, -10, 1, 13, 25, 38, 53, 69, 89, 113};
+            const bool one = type == GGML_TYPE_Q4_1 || type == GGML_TYPE_Q5_1, five = type == GGML_TYPE_Q5_0 || type == GGML_TYPE_Q5_1;
+            uint16_t hd, hm = 0;
+            uint32_t qh = 0;
+            memcpy(&hd, p, 2);
+            if (one) memcpy(&hm, p + 2, 2);
+            if (five) memcpy(&qh, p + (one ? 4 : 2), 4);
+            const uint8_t * qs = p + 2 + (one ? 2 : 0) + (five ? 4 : 0);
+            const float d = f16_to_f32(hd), m = f16_to_f32(hm);
+            for (int j = 0; j < 32; ++j) {
+                int q = j < 16 ? (qs[j] & 0xF) : (qs[j - 16] >> 4);
+                if (five) q |= (int) ((qh >> j) & 1u) << 4;
+                if (type == GGML_TYPE_IQ4_NL) y[j] = d * (float) iq4nl[q];
+                else if (one) y[j] = (float) q * d + m;
+                else y[j] = (float) (q - (five ? 16 : 8)) * d;
             }
         } break;
         default: LLM_ASSERT(!"block_values: unsupported type");
@@ -316,6 +346,9 @@ extern "C" int llm_preset(const char * name, struct llm_hparams * hp) {
     else if (n == "test-llama-tp") set("llama", 2, 512, 8, 4, 64, 1024, 512, 512, 10000.0f, 1e-5f, 0, 0, LLM_FTYPE_MIXED);
     // four-way tensor split with head_dim 128: 8 heads on 4 KV heads (2 + 1 per rank), wo K slices of 256, ffn_down K slices of 512, 1024 vocab rows per rank
     else if (n == "test-llama-tp4") set("llama", 2, 1024, 8, 4, 128, 2048, 4096, 512, 10000.0f, 1e-5f, 0, 0, LLM_FTYPE_MIXED);
+    else if (n == "test-llama-legacy") set("llama", 3, 256, 4, 2, 64, 512, 512, 512, 10000.0f, 1e-5f, 0, 0, LLM_FTYPE_MIXED_LEGACY);
+    else if (n == "test-qwen2-legacy") set("qwen2", 2, 256, 4, 2, 64, 768, 768, 512, 1000000.0f, 1e-6f, GGML_ROPE_TYPE_NEOX, 1, LLM_FTYPE_MIXED_LEGACY);
+    else if (n == "llama2-7b-q4_0") set("llama", 32, 4096, 32, 32, 128, 11008, 32000, 4096, 10000.0f, 1e-5f, 0, 0, LLM_FTYPE_Q4_0);
     else if (n == "test-qwen2") set("qwen2", 2, 256, 4, 2, 64, 768, 768, 512, 1000000.0f, 1e-6f, GGML_ROPE_TYPE_NEOX, 1, LLM_FTYPE_MIXED);
     else return -1;
     return 0;
@@ -380,6 +413,17 @@ static ggml_type pick_type(const llm_hparams & hp, const char * what, int il) {
             unsigned h = (unsigned) il * 7u;
             for (char c : w) h = h * 31u + (unsigned char) c;
             return cyc[h % 4];
+        }
+        case LLM_FTYPE_Q4_0: return w == "output" ? GGML_TYPE_Q6_K : GGML_TYPE_Q4_0;
+        case LLM_FTYPE_Q4_1: return w == "output" ? GGML_TYPE_Q6_K : GGML_TYPE_Q4_1;
+        case LLM_FTYPE_Q5_0: return w == "output" ? GGML_TYPE_Q6_K : GGML_TYPE_Q5_0;
+        case LLM_FTYPE_Q5_1: return w == "output" ? GGML_TYPE_Q6_K : GGML_TYPE_Q5_1;
+        case LLM_FTYPE_IQ4_NL: return w == "output" ? GGML_TYPE_Q6_K : GGML_TYPE_IQ4_NL;
+        case LLM_FTYPE_MIXED_LEGACY: {
+            static const ggml_type cyc[6] = {GGML_TYPE_Q4_0, GGML_TYPE_Q4_1, GGML_TYPE_Q5_0, GGML_TYPE_Q5_1, GGML_TYPE_IQ4_NL, GGML_TYPE_Q8_0};
+            unsigned h = (unsigned) il * 7u;
+            for (char c : w) h = h * 31u + (unsigned char) c;
+            return cyc[h % 6];
         }
         default: return GGML_TYPE_Q8_0;
     }

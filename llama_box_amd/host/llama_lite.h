@@ -25,6 +25,13 @@ enum llm_ftype {
     LLM_FTYPE_Q6_K = 3,    /* everything Q6_K */
     LLM_FTYPE_F16 = 4,     /* everything F16 */
     LLM_FTYPE_MIXED = 5,   /* test recipe: cycles Q4_K/Q5_K/Q6_K/Q8_0 over tensors so one tiny model hits every kernel */
+    /* the 4- and 5-bit formats of 32-value blocks, as llama.cpp writes such files: the base format everywhere (token_embd included), output.weight Q6_K */
+    LLM_FTYPE_Q4_0 = 6,
+    LLM_FTYPE_Q4_1 = 7,
+    LLM_FTYPE_Q5_0 = 8,
+    LLM_FTYPE_Q5_1 = 9,
+    LLM_FTYPE_IQ4_NL = 10,
+    LLM_FTYPE_MIXED_LEGACY = 11, /* test recipe: cycles Q4_0/Q4_1/Q5_0/Q5_1/IQ4_NL/Q8_0 over the tensors of one tiny model */
 };
 
 struct llm_hparams {
