@@ -158,6 +158,7 @@ struct stats {
     int64_t wide_launches = 0;         // prompt-batch mat-muls served by its wide form
     int64_t tiled_launches = 0;        // batch mat-muls served by the LDS-tiled int8 GEMM (mmq_i8.hip)
     int64_t nf_mma_chains = 0;         // non-flash K.q -> SOFT_MAX -> V^T.p chains of a prompt micro-batch served by the two-pass matrix-core kernel (round 4)
+    int64_t fa_form = 0;               // kernels.h fa_form_code of the last FLASH_ATTN_EXT node of the graph computed last (0: it had none)
     int64_t fa_list_launches = 0;      // FLASH_ATTN_EXT nodes served over per-token position lists (2..32 tokens; 33..256 when the mask is known to be sparse)
     int64_t rope_epilogues = 0;        // batches whose rope + KV-cache stores rode in the skinny QKV launches
     int64_t graph_launch_host_ns = 0;  // host time spent inside hipGraphLaunch (replays only)
@@ -192,6 +193,7 @@ struct cached_graph {
     uint64_t last_use = 0;
     int64_t allreduces = 0;  // reductions / collectives recorded in the graph (counted again at every replay: stats::allreduces)
     int n_nodes = 0;
+    int fa_form = 0;  // stats::fa_form as the capture walk left it (reported again at every replay)
     bool early_failed = false;  // a capture at first sighting was tried and failed (graph.cpp)
     std::vector<uint64_t> key;  // the graph this entry stands for, word by word (graph.cpp: walk_key) — an entry is used only when these are equal
 };

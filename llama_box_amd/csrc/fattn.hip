@@ -31,6 +31,9 @@ static inline bool fa_g_ok(const int64_t G) {
 }
 static inline int fa_gg(const int64_t G) { return G <= 2 ? 2 : (G <= 4 ? 4 : 8); }
 
+thread_local int g_fa_form = 0;  // kernels.h: the form of this thread's last attention launch (host-side note)
+static inline void fa_form_tail(int tail) { g_fa_form = (g_fa_form & ~(7 << 13)) | (tail << 13); }
+
 struct fa_geom {
     int n_q, n_head, n_kv_head, n_kv, n_splits, has_mask;
     int rec_stride;  // floats between the partial records of consecutive splits (D + 2; 132 for the records the wo prologue reads)
@@ -1063,6 +1066,7 @@ void launch_flash_attn_combine(hipStream_t s, int D, const float * ws, const flo
     if (fattn_combine_rows_applies(D, n_q, n_head, n_batch, n_splits, sinks) && (((uintptr_t) ws) & 7) == 0 &&
         (q8_out ? (n_head % 2) == 0 : ((dst.nb[1] % 16) == 0 && (dst.nb[2] % 16) == 0 && (dst.nb[3] % 16) == 0 && (((uintptr_t) dst.data) & 15) == 0))) {
         const unsigned blocks = (unsigned) ((n_rows + 7) / 8);
+        fa_form_tail(FA_FORM_TAIL_COMBINE_ROWS);
         if (q8_out) {
             if (n_splits <= 4) hipLaunchKernelGGL((k_fattn_combine_rows<128, 4, true>), dim3(blocks), dim3(256), 0, s, ws, dst, geo, (int) n_rows, (q8k_dev *) q8_out);
             else hipLaunchKernelGGL((k_fattn_combine_rows<128, 8, true>), dim3(blocks), dim3(256), 0, s, ws, dst, geo, (int) n_rows, (q8k_dev *) q8_out);
@@ -1073,6 +1077,7 @@ void launch_flash_attn_combine(hipStream_t s, int D, const float * ws, const flo
         return;
     }
     dim3 g2((unsigned) n_head, (unsigned) n_q, (unsigned) n_batch);
+    fa_form_tail(FA_FORM_TAIL_COMBINE);
     if (q8_out && D == 128) {
         hipLaunchKernelGGL((k_fattn_combine<128, true>), dim3((unsigned) (n_head / 2), (unsigned) n_q, (unsigned) n_batch), dim3(256), 0, s, ws, sinks, dst, geo, (q8k_dev *) q8_out);
         return;
@@ -1165,6 +1170,7 @@ __global__ void __launch_bounds__(256) k_q8_0_rows_to_f16(const tdesc k, const t
 template <int D, int G> static void launch_fa(hipStream_t s, const tdesc & q, const tdesc & k, const tdesc & v, const tdesc & mask, const float * sinks,
                                               const tdesc & dst, const fa_geom & geo, float * ws) {
     dim3 grid((unsigned) geo.n_splits, (unsigned) geo.n_kv_head, (unsigned) (geo.n_q * q.ne[3]));
+    g_fa_form = fa_form_code(FA_FORM_K_SPLIT, 0, 4, FA_FORM_KV_F16, D, geo.n_splits > 1 ? FA_FORM_TAIL_COMBINE : FA_FORM_TAIL_NONE);
     hipLaunchKernelGGL((k_fattn_split<D, G>), grid, dim3(256), 0, s, q, k, v, mask, sinks, dst, geo, ws);
     if (geo.n_splits > 1) {
         dim3 g2((unsigned) geo.n_head, (unsigned) geo.n_q, (unsigned) q.ne[3]);
@@ -1286,7 +1292,10 @@ void launch_flash_attn(hipStream_t s, const tdesc & q, const tdesc & k, const td
         }
         fattn_params p16 = p;
         p16.kv_type = GGML_TYPE_F16;
-        if (launch_flash_attn_mma(s, q, k16, v16, mask, sinks, dst, p16, workspace)) return;
+        if (launch_flash_attn_mma(s, q, k16, v16, mask, sinks, dst, p16, workspace)) {
+            g_fa_form |= FA_FORM_KV_Q8_IMAGE << 10;
+            return;
+        }
         MI_ERR("launch_flash_attn: the matrix-core kernel refused a batch flash_attn_mma_applies accepted");
         abort();
     }
@@ -1317,6 +1326,7 @@ void launch_flash_attn(hipStream_t s, const tdesc & q, const tdesc & k, const td
             // one decode token, few fat splits on 8-wave workgroups; the partial records stay in the workspace for the wo prologue
             if (q8 || p.dq || geo.n_q != 1 || q.ne[3] != 1 || sinks != nullptr) { MI_ERR("launch_flash_attn: fat-split form requested for a case it does not serve"); abort(); }
             geo.rec_stride = FA_REC;
+            g_fa_form = fa_form_code(FA_FORM_K_DEC, FA_FORM_MODE_PLAIN, 8, FA_FORM_KV_F16, 128, FA_FORM_TAIL_FAT);
             if (fa_gg(G) == 2) hipLaunchKernelGGL((k_fattn_dec128<2, 0, false, 8>), grid, dim3(512), 0, s, q, k, v, mk, sinks, dst, geo, ws, G, nullptr, 0);
             else if (fa_gg(G) == 4) hipLaunchKernelGGL((k_fattn_dec128<4, 0, false, 8>), grid, dim3(512), 0, s, q, k, v, mk, sinks, dst, geo, ws, G, nullptr, 0);
             else hipLaunchKernelGGL((k_fattn_dec128<8, 0, false, 8>), grid, dim3(512), 0, s, q, k, v, mk, sinks, dst, geo, ws, G, nullptr, 0);
@@ -1369,6 +1379,8 @@ void launch_flash_attn(hipStream_t s, const tdesc & q, const tdesc & k, const td
     }
         geo.arrive = self_merge ? p.arrive : nullptr;
         geo.merge2 = merge2 ? 1 : 0;
+        g_fa_form = fa_form_code(FA_FORM_K_DEC, list ? FA_FORM_MODE_LIST : (skip ? FA_FORM_MODE_SKIP : FA_FORM_MODE_PLAIN), (wide8 || list8) ? 8 : 4,
+                                 dq ? FA_FORM_KV_BLOCK : (q8 ? FA_FORM_KV_Q8_0 : FA_FORM_KV_F16), 128, merge2 ? FA_FORM_TAIL_MERGE2 : (self_merge ? FA_FORM_TAIL_SELF_MERGE : FA_FORM_TAIL_NONE));
         geo.q8 = (self_merge || (geo.n_splits == 1 && !(G & 1))) ? p.q8_out : nullptr;
         geo.per = skip ? per : (geo.n_kv + geo.n_splits - 1) / geo.n_splits;
         {
@@ -1421,6 +1433,7 @@ void launch_flash_attn(hipStream_t s, const tdesc & q, const tdesc & k, const td
         const bool list = p.lists != nullptr;  // (2 .. 32 tokens of a -np decode step: each walks the list of its own visible cells, as at head_dim 128)
         const int lstride = geo.n_kv + 1;
         const bool wide = !list && geo.n_splits > 1;  // (eight waves: a trip covers 64 / 128 cells)
+        g_fa_form = fa_form_code(FA_FORM_K_DEC, list ? FA_FORM_MODE_LIST : FA_FORM_MODE_PLAIN, wide ? 8 : 4, FA_FORM_KV_F16, 64, FA_FORM_TAIL_NONE);
         for (int64_t b = 0; b < q0.ne[3]; ++b) {  // one launch per batch slice: the kernel has no batch arithmetic
             tdesc qb = q0, kb = k0, vb = v0, mb = mk0, db = dst0;
             qb.data += b * q0.nb[3];

@@ -640,6 +640,7 @@ bool launch_flash_attn_mma(hipStream_t s, const tdesc & q, const tdesc & k, cons
     const int tiles_all = (geo.n_kv + 63) / 64, tps = (tiles_all + geo.n_splits - 1) / geo.n_splits;
     const uint8_t * const tile_vis = tps <= 16384 ? p.tile_vis : nullptr;  // (without the states every tile is multiplied and reads its mask: correct, slower)
     const size_t vt_bytes = tile_vis ? (size_t) ((tps + 15) & ~15) : 0;  // the split's tile states (a byte per tile)
+    g_fa_form = fa_form_code(FA_FORM_K_MMA, tile_vis ? 1 : 0, nw, FA_FORM_KV_F16, D, FA_FORM_TAIL_NONE);  // (the combine pass adds which kernel merges)
     if (D == 128) {
         const size_t lds = 64 * (128 + 8) * 2 + 128 * (64 + 4) * 2 + vt_bytes;
         if (nw == 4) hipLaunchKernelGGL((k_fattn_mma<128, 4>), grid, dim3(256), lds, s, q, k, v, mk, dst, geo, ws, tile_vis);

@@ -2282,7 +2282,9 @@ static int run_node(exec_state & st, int i) {
                     p.n_splits = S;
                     p.fat = 1;
                     timed_scope ts(c, "flash_attn_fat", (double) (k->ne[1] * k->ne[2] * k->ne[0] * 2 * 2));
+                    g_fa_form = 0;
                     launch_flash_attn(s, qd, kd, vd, m ? &md : nullptr, nullptr, TD(n), p, (char *) c->ws + st.aux_off);
+                    c->st.fa_form = g_fa_form;
                     st.fa_wo.b = view;
                     st.fa_wo.fa = n;
                     st.fa_wo.part = (const float *) ((char *) c->ws + st.aux_off);
@@ -2311,7 +2313,9 @@ static int run_node(exec_state & st, int i) {
                 }
             }
             if (q8_reader) p.q8_out = (char *) c->ws + st.act_off;
+            g_fa_form = 0;
             launch_flash_attn(s, qd, kd, vd, m ? &md : nullptr, n->src[4] ? (const float *) n->src[4]->data : nullptr, TD(n), p, (char *) c->ws + st.aux_off);
+            c->st.fa_form = g_fa_form;
             if (q8_reader) {
                 mark_q8_cache(st, q8_reader);
                 c->st.fused_nodes++;
@@ -2467,6 +2471,7 @@ enum ggml_status graph_compute(backend_ctx * c, ggml_cgraph * g) {
         ~host_clock() { c->st.graph_compute_host_ns += std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count(); }
     } clock{c, t_enter};
     c->tick++;
+    c->st.fa_form = 0;  // (the attention form of THIS graph: set by its walk, or by the replay below from what the capture walk noted)
     {   // a decode copy was dropped since the cached graphs were captured (the host rewrote a weight, freed a weights buffer): they hold pointers to it
         const uint64_t ep = decode_copy_epoch();
         if (ep != c->decode_epoch) {
@@ -2489,6 +2494,7 @@ enum ggml_status graph_compute(backend_ctx * c, ggml_cgraph * g) {
         c->st.graph_launch_host_ns += std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
         c->st.graph_launches++;
         c->st.allreduces += cg.allreduces;
+        c->st.fa_form = cg.fa_form;
         return GGML_STATUS_SUCCESS;
     };
     // the step llama-box repeats: the same graph as last time.  Its key is compared in place; an instantiated graph implies that the scratch it was
@@ -2596,6 +2602,7 @@ enum ggml_status graph_compute(backend_ctx * c, ggml_cgraph * g) {
     const int64_t red0 = c->st.allreduces;
     const bool ok = run_nodes(c, g, wp);
     c->capturing = false;
+    cg.fa_form = (int) c->st.fa_form;
     const int64_t red_captured = c->st.allreduces - red0;
     hipGraph_t graph = nullptr;
     const hipError_t e_end = hipStreamEndCapture(c->stream, &graph);
