@@ -392,6 +392,21 @@ __device__ unsigned long long g_fa_stamps[1024][8];
 #else
 #define FA_STAMP_AT(i)
 #endif
+// Round 7 (-DFA_KV_NT=0 for an A/B build): non-temporal K / V row loads in the one-token eight-wave f16 form — every cached byte is read once per layer
+// (the forms for several tokens re-read rows from L2: never there)
+#ifndef FA_KV_NT
+#define FA_KV_NT 1
+#endif
+// Round 7 (-DFA_MASK_LATE=0 for an A/B build): a trip's mask value stays its f16 bits until the score is masked; converted where it was loaded, the conversion's
+// wait (vmcnt 0) stood between a trip's K / V requests and whatever is requested next — in the first trip the query, a second round trip for every workgroup
+#ifndef FA_MASK_LATE
+#define FA_MASK_LATE 1
+#endif
+typedef uint32_t fa_u32x4 __attribute__((ext_vector_type(4)));
+static __device__ __forceinline__ uint4 fa_ld_nt16(const char * p) {
+    const fa_u32x4 r = __builtin_nontemporal_load((const fa_u32x4 *) p);
+    return make_uint4(r.x, r.y, r.z, r.w);
+}
 // SKIP = true (several query tokens, e.g. -np 32 decode over a unified cache where each token sees ~1/32 of the cells): the mask
 // of the whole split is read first — one round trip — and trips without a visible position for this wave load no K/V at all.
 // Q8 = true: K and V rows are block_q8_0 (quantised KV cache, -ctk/-ctv q8_0).  As in ggml-cpu the query is quantised to Q8_0
@@ -453,16 +468,26 @@ __global__ void __launch_bounds__(WV * 64) k_fattn_dec128(const tdesc q, const t
     // LIST: the list entries of the NEXT trip to be loaded (one per row group u), requested a round trip before its K/V rows are — for one
     // split together with the count itself, so that neither the count nor the entries sit in the chain count -> entries -> rows that
     // every trip used to walk (entries past the count are stale: they are replaced by the first entry, a visible cell, before use)
-    int nidx[NG];
+    int nidx[NG] = {};
     int first = 0;
-#define FA_LIST_AHEAD(base)                                                                                         \
+    // LIVE ROW GROUPS (round 7): a wave-instruction costs the CU's address pipe the same whether its lanes fetch RPW rows or one clamped row RPW times, so
+    // row group u of the trip at `base` is requested by a wave only if the wave's FIRST row of it, base + u * WV * RPW + wave * RPW, lies before the split's end
+    // (LIST: before the list's) — a scalar condition; a partly live group keeps the clamp.  A dead group loads no K, V or list entry, its dot products and its
+    // P.V terms are skipped: its pairs are masked (okl) and had probability 0 before, so the live pairs keep their sums and their order.
+    // Not in SKIP mode: its splits are whole multiples of 64 cells (dead groups only at the cache's end), and the branches around the row groups took its
+    // forms from 184 .. 278 to 214 .. 348 VGPRs — past 256 a CU holds one of its workgroups instead of two.  There every group is loaded (clamped) and computed.
+    const int wrow = __builtin_amdgcn_readfirstlane(wave) * RPW;
+#define FA_LIVE(base, u) (SKIP || (base) + (u) * (WV * RPW) + wrow < kv1)
+#define FA_LIST_AHEAD_ALL(base)                                                                                     \
     _Pragma("unroll") for (int u = 0; u < NG; ++u) nidx[u] = tl[min((base) + u * (WV * RPW) + wave * RPW + sub, geo.n_kv - 1)];
+#define FA_LIST_AHEAD(base)                                                                                         \
+    _Pragma("unroll") for (int u = 0; u < NG; ++u) if (FA_LIVE(base, u)) nidx[u] = tl[min((base) + u * (WV * RPW) + wave * RPW + sub, geo.n_kv - 1)];
     if constexpr (LIST) {
         const int * lt = lists + (int64_t) tok * list_stride;
         tl = lt + 1;
         cnt = lt[0];
         first = lt[1];
-        if (geo.n_splits == 1) FA_LIST_AHEAD(0)
+        if (geo.n_splits == 1) FA_LIST_AHEAD_ALL(0)  // (requested together with the count: not yet known)
         const int trips = (cnt + TRIP - 1) / TRIP, share = (trips + geo.n_splits - 1) / geo.n_splits;
         ti = split * share;
         ti1 = min(trips, ti + share);
@@ -513,11 +538,12 @@ __global__ void __launch_bounds__(WV * 64) k_fattn_dec128(const tdesc q, const t
     // a trip covers NG*16 consecutive positions: position of (u, wave, sub) = p0 + u*16 + wave*4 + sub
     uint4 kraw[NG], vraw[NG];
     float mvl = 0.0f;   // mask value / validity of THIS lane's pair (ul, sub)
+    uint16_t mrl = 0;   // (FA_MASK_LATE: its f16 bits, converted where the score is masked)
     bool okl = false;
     int p0 = LIST ? ti * TRIP : kv0;
 #define FA_LOAD_TRIP()                                                                  \
     {                                                                                   \
-        _Pragma("unroll") for (int u = 0; u < NG; ++u) {                               \
+        _Pragma("unroll") for (int u = 0; u < NG; ++u) if (FA_LIVE(p0, u)) {           \
             const int pr_ = p0 + u * (WV * RPW) + wave * RPW + sub;                     \
             const int pc = LIST ? (pr_ < kv1 ? nidx[u] : first) : min(pr_, kv1 - 1);    \
             const char * kp_ = kbase + (int64_t) pc * k.nb[1];                          \
@@ -528,12 +554,15 @@ __global__ void __launch_bounds__(WV * 64) k_fattn_dec128(const tdesc q, const t
             } else if constexpr (Q8) {  /* 8 quants (2-byte aligned) + the block's f16 scale */  \
                 kraw[u] = make_uint4(ld32_a2(kp_), ld32_a2(kp_ + 4), (uint32_t) ld16(kp_ - 2 - (sl & 3) * 8), 0u);  \
                 vraw[u] = make_uint4(ld32_a2(vp_), ld32_a2(vp_ + 4), (uint32_t) ld16(vp_ - 2 - (sl & 3) * 8), 0u);  \
+            } else if constexpr (FA_KV_NT != 0 && FAT && !BF) {  /* one token reads every cached byte once per layer */ \
+                kraw[u] = fa_ld_nt16(kp_);                                              \
+                vraw[u] = fa_ld_nt16(vp_);                                              \
             } else {                                                                    \
                 kraw[u] = *(const uint4 *) kp_;                                         \
                 vraw[u] = *(const uint4 *) vp_;                                         \
             }                                                                           \
         }                                                                               \
-        const int pl = p0 + ul * (WV * RPW) + wave * RPW + sub;                         \
+        const int pl = p0 + ul * (WV * RPW) + wave * RPW + sub;                        \
         okl = pl < kv1;                                                                 \
         int plc_ = min(pl, kv1 - 1);                                                    \
         if constexpr (LIST) {                                                           \
@@ -541,7 +570,8 @@ __global__ void __launch_bounds__(WV * 64) k_fattn_dec128(const tdesc q, const t
             _Pragma("unroll") for (int u = 1; u < NG; ++u) plc_ = ul == u ? nidx[u] : plc_; \
             plc_ = okl ? plc_ : first;                                                  \
         }                                                                               \
-        mvl = mp ? h2f(mp[plc_]) : 0.0f;                                                \
+        if constexpr (FA_MASK_LATE != 0) mrl = mp ? mp[plc_] : (uint16_t) 0;            \
+        else mvl = mp ? h2f(mp[plc_]) : 0.0f;                                           \
         if constexpr (LIST) FA_LIST_AHEAD(p0 + TRIP)                                    \
     }
     uint32_t vis = 0xFFFFFFFFu;  // bit i: trip i has a position this wave can see
@@ -649,8 +679,14 @@ __global__ void __launch_bounds__(WV * 64) k_fattn_dec128(const tdesc q, const t
         // ---- partial dots of this lane's 8 dims for the 16 (u, g) pairs
         float t[LPR];
         float vf[NG][8];
+        const int rem = SKIP ? NG * WV * RPW : kv1 - p0 - wrow;  // row group u of THIS trip is live for the wave iff u * WV * RPW < rem (FA_LIVE when it was loaded)
 #pragma unroll
         for (int u = 0; u < NG; ++u) {
+            if (u * (WV * RPW) >= rem) {  // dead: nothing was loaded; its pairs enter the reduce as zeros and leave it masked
+#pragma unroll
+                for (int g = 0; g < G; ++g) t[u * G + g] = 0.0f;
+                continue;
+            }
             uint32_t ku[4] = {kraw[u].x, kraw[u].y, kraw[u].z, kraw[u].w}, vu[4] = {vraw[u].x, vraw[u].y, vraw[u].z, vraw[u].w};
             if constexpr (DQ) {
                 // ggml-cpu's arithmetic for a block-format cache (round 6): integer block dots of K's levels with the Q8_0 / Q8_1 query, one f32 term per
@@ -722,10 +758,15 @@ __global__ void __launch_bounds__(WV * 64) k_fattn_dec128(const tdesc q, const t
         if (trip == 0) { asm volatile("" :: "v"(t[0]), "v"(t[15])); FA_STAMP_AT(3) }  // the first trip's K has arrived and its dot products are done
 #endif
         const bool more = p_next < kv1 && (!SKIP || ((vis >> (trip + 1)) & 1u));
-        const float mv_cur = mvl;
+        const float mv_cur = FA_MASK_LATE != 0 ? h2f(mrl) : mvl;
         const bool ok_cur = okl;
         p0 = p_next;  // (nothing below uses the current trip's position)
-        if (more) FA_LOAD_TRIP()  // long splits: the next trip's loads go out before the reductions
+        if (more) {  // long splits: the next trip's loads go out before the reductions
+            // (every load of THIS trip has been consumed above or was never issued; said aloud, because the wait-count pass cannot know that a group whose
+            //  use is skipped was not loaded either: it would wait for the younger loads of the next trip before each write of a dead group's registers)
+            if constexpr (!SKIP) __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
+            FA_LOAD_TRIP()
+        }
         // ---- transpose-reduce over the 16 lanes of the row: lane j ends with the complete dot of pair j
         float w8[8], w4[4], w2[2];
 #pragma unroll
@@ -785,17 +826,24 @@ __global__ void __launch_bounds__(WV * 64) k_fattn_dec128(const tdesc q, const t
         const float pj_ = (lane & 8) ? pb_ : pa_;                                           \
         _Pragma("unroll") for (int i = 0; i < 8; ++i) acc[(j) % G][i] = fmaf(pj_, vf[(j) / G][i], acc[(j) % G][i]); \
     }
-        if constexpr (LPR == 16) {
-            FA_PAIR(0) FA_PAIR(1) FA_PAIR(2) FA_PAIR(3) FA_PAIR(4) FA_PAIR(5) FA_PAIR(6) FA_PAIR(7)
-            FA_PAIR(8) FA_PAIR(9) FA_PAIR(10) FA_PAIR(11) FA_PAIR(12) FA_PAIR(13) FA_PAIR(14) FA_PAIR(15)
-        } else {
-            FA_PAIR8(0) FA_PAIR8(1) FA_PAIR8(2) FA_PAIR8(3) FA_PAIR8(4) FA_PAIR8(5) FA_PAIR8(6) FA_PAIR8(7)
-        }
+        // (pairs in ascending order as before, row group by row group; a dead group's probabilities are 0 and its V registers hold nothing: skipped)
+#define FA_PAIR_G(u, g) if constexpr ((g) < G) { if constexpr (LPR == 16) FA_PAIR((u) * G + (g)) else FA_PAIR8((u) * G + (g)) }
+#define FA_GROUP(u)                                                                         \
+    if constexpr ((u) < NG) {                                                               \
+        if ((u) * (WV * RPW) < rem) {                                                       \
+            FA_PAIR_G(u, 0) FA_PAIR_G(u, 1) FA_PAIR_G(u, 2) FA_PAIR_G(u, 3) FA_PAIR_G(u, 4) FA_PAIR_G(u, 5) FA_PAIR_G(u, 6) FA_PAIR_G(u, 7) \
+        }                                                                                   \
+    }
+        FA_GROUP(0) FA_GROUP(1) FA_GROUP(2) FA_GROUP(3) FA_GROUP(4) FA_GROUP(5) FA_GROUP(6) FA_GROUP(7)
+#undef FA_GROUP
+#undef FA_PAIR_G
 #undef FA_PAIR8
 #undef FA_PAIR
     }
 #undef FA_LOAD_TRIP
 #undef FA_LIST_AHEAD
+#undef FA_LIST_AHEAD_ALL
+#undef FA_LIVE
 #ifdef FA_STAMP
     asm volatile("" :: "v"(acc[0][0]), "v"(acc[G - 1][7]));
     FA_STAMP_AT(4)
@@ -1108,6 +1156,8 @@ int fattn_pick_splits(const tdesc & q, const tdesc & k, const tdesc * mask, int 
         const int64_t by_len = (n_kv + 255) / 256;
         return (int) std::max<int64_t>(1, std::min<int64_t>(64, std::min<int64_t>(by_len, std::max<int64_t>(1, n_kv / 64))));
     }
+    // (round 7, dead row groups no longer loaded: 32 splits instead of 26 at the bench's 2304 cells take the split kernel from 6.45 to 6.38 us per layer, 0.1 % of a
+    // step before the six extra records per head reach the combine pass — round 6 had 32 splits 0.8 % behind 24; the three constants stay: profiles/r07_fa_live_groups_ab.txt)
     const int64_t groups = k.ne[2] * q.ne[1] * q.ne[3];
     int64_t want = (768 + groups - 1) / groups;  // ~3 workgroups per CU
     const int64_t max_by_len = std::max<int64_t>(1, n_kv / 86);  // (~1.4 trips of 64 cells per split: 24 splits at 2 100 cells measure 0.8 % of a decode step ahead of 32 — fewer records for the combine pass)
