@@ -456,6 +456,9 @@ typedef struct { ggml_fp16_t d; uint8_t qh[4]; uint8_t qs[16]; } block_q5_0;    
 typedef struct { ggml_fp16_t d; ggml_fp16_t m; uint8_t qh[4]; uint8_t qs[16]; } block_q5_1;                /* 24 B */
 typedef struct { ggml_fp16_t d; ggml_fp16_t s; int8_t qs[32]; } block_q8_1;                                /* 36 B: s = d * sum(qs) */
 typedef struct { ggml_fp16_t d; uint8_t qs[16]; } block_iq4_nl;                                            /* 18 B */
+/* Q2_K: scales[j] = 4-bit scale | 4-bit min << 4 of the 16-value sub-block j; Q3_K: hmask bit CLEAR = level - 4, 16 six-bit scales in 12 bytes used as sc - 32 */
+typedef struct { uint8_t scales[QK_K / 16]; uint8_t qs[QK_K / 4]; ggml_fp16_t d; ggml_fp16_t dmin; } block_q2_K;      /* 84 B */
+typedef struct { uint8_t hmask[QK_K / 8]; uint8_t qs[QK_K / 4]; uint8_t scales[K_SCALE_SIZE]; ggml_fp16_t d; } block_q3_K; /* 110 B */
 typedef struct { ggml_fp16_t d; ggml_fp16_t dmin; uint8_t scales[K_SCALE_SIZE]; uint8_t qs[QK_K / 2]; } block_q4_K;   /* 144 B */
 typedef struct { ggml_fp16_t d; ggml_fp16_t dmin; uint8_t scales[K_SCALE_SIZE]; uint8_t qh[QK_K / 8]; uint8_t qs[QK_K / 2]; } block_q5_K; /* 176 B */
 typedef struct { uint8_t ql[QK_K / 2]; uint8_t qh[QK_K / 4]; int8_t scales[QK_K / 16]; ggml_fp16_t d; } block_q6_K;   /* 210 B */
@@ -465,6 +468,8 @@ typedef struct { float d; int8_t qs[QK_K]; int16_t bsums[QK_K / 16]; } block_q8_
 #ifdef __cplusplus
 static_assert(sizeof(block_q8_0) == 34, "q8_0");
 static_assert(sizeof(block_q4_0) == 18 && sizeof(block_q4_1) == 20 && sizeof(block_q5_0) == 22 && sizeof(block_q5_1) == 24 && sizeof(block_q8_1) == 36 && sizeof(block_iq4_nl) == 18, "legacy 32-value blocks");
+static_assert(sizeof(block_q2_K) == 84, "q2_K");
+static_assert(sizeof(block_q3_K) == 110, "q3_K");
 static_assert(sizeof(block_q4_K) == 144, "q4_K");
 static_assert(sizeof(block_q5_K) == 176, "q5_K");
 static_assert(sizeof(block_q6_K) == 210, "q6_K");
@@ -480,7 +485,7 @@ static_assert(sizeof(struct ggml_tensor) % GGML_MEM_ALIGN == 0, "ggml_tensor ali
 static inline int64_t ggml_abi_blck_size(enum ggml_type t) {
     switch (t) {
         case GGML_TYPE_Q8_0: case GGML_TYPE_Q4_0: case GGML_TYPE_Q4_1: case GGML_TYPE_Q5_0: case GGML_TYPE_Q5_1: case GGML_TYPE_Q8_1: case GGML_TYPE_IQ4_NL: return 32;
-        case GGML_TYPE_Q4_K: case GGML_TYPE_Q5_K: case GGML_TYPE_Q6_K: case GGML_TYPE_Q8_K: return 256;
+        case GGML_TYPE_Q2_K: case GGML_TYPE_Q3_K: case GGML_TYPE_Q4_K: case GGML_TYPE_Q5_K: case GGML_TYPE_Q6_K: case GGML_TYPE_Q8_K: return 256;
         default: return 1;
     }
 }
@@ -496,6 +501,8 @@ static inline size_t ggml_abi_type_size(enum ggml_type t) {
         case GGML_TYPE_Q5_0: return 22;
         case GGML_TYPE_Q5_1: return 24;
         case GGML_TYPE_Q8_1: return 36;
+        case GGML_TYPE_Q2_K: return 84;
+        case GGML_TYPE_Q3_K: return 110;
         case GGML_TYPE_Q4_K: return 144;
         case GGML_TYPE_Q5_K: return 176;
         case GGML_TYPE_Q6_K: return 210;

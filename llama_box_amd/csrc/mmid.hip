@@ -160,6 +160,8 @@ void launch_mmid(hipStream_t s, const mmid_args & a) {
         abort();
     }
     switch (a.type) {
+        case GGML_TYPE_Q2_K: launch_mmid_t<T_Q2K>(s, a); break;
+        case GGML_TYPE_Q3_K: launch_mmid_t<T_Q3K>(s, a); break;
         case GGML_TYPE_Q4_K: launch_mmid_t<T_Q4K>(s, a); break;
         case GGML_TYPE_Q5_K: launch_mmid_t<T_Q5K>(s, a); break;
         case GGML_TYPE_Q6_K: launch_mmid_t<T_Q6K>(s, a); break;

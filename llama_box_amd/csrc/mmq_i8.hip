@@ -1,5 +1,5 @@
 // mmq_i8.hip — batched mat-mul (3 columns and up: continuous-batching decode steps, prompt micro-batches) for Q4_K, Q5_K and
-// Q6_K weights on the gfx950 INTEGER matrix cores.
+// Q6_K weights — and, from 9 columns, Q2_K (one piece, sc * level) and Q3_K (two: the level is split) — on the gfx950 INTEGER matrix cores.
 //
 // Same contract as mmq.hip (ggml-cpu's ggml_vec_dot_q{4,5}_K_q8_K: integer block sums on Q8_K activations, one f32
 // scale-accumulate per super-block — SURVEY.md §8a row a6), but the block sums are computed by v_mfma_i32_32x32x32_i8:
@@ -60,9 +60,11 @@ template <int QT, int BN, int BM = 128>
 __global__ void __launch_bounds__(BN * 4, BN == 64 ? (BM == 32 ? 3 : 2) : 1) k_mmq_i8(const mmq8_args a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int NT = BN * 4;
-    constexpr int NP = QT == 5 ? 3 : 2;
-    constexpr int BYTES = QT == 4 ? 144 : (QT == 5 ? 176 : 210);
-    constexpr bool Q6 = QT == 6;
+    constexpr int NP = QT == 5 ? 3 : (QT == 2 ? 1 : 2);
+    constexpr int BYTES = QT == 2 ? 84 : (QT == 3 ? 110 : (QT == 4 ? 144 : (QT == 5 ? 176 : 210)));
+    constexpr bool Q6 = QT == 6, Q2 = QT == 2, Q3 = QT == 3;
+    constexpr bool NIB = QT == 4 || QT == 5;  // nibble formats: 32-value sub-blocks, digits of the scale
+    constexpr bool NOMIN = Q6 || Q3;          // no mins term: the 16-wide f16 step is skipped
     constexpr int TA = BN * 128, TB = BM * 128, STAGE = NP * TA + TB;
     constexpr int NBC = (BM * 8) / NT;  // 16-byte activation chunks per thread per trip (1, 2 or 4)
     constexpr int NTT = BM >= 64 ? 2 : 1;  // 32-column tiles per wave
@@ -125,10 +127,26 @@ __global__ void __launch_bounds__(BN * 4, BN == 64 ? (BM == 32 ? 3 : 2) : 1) k_m
     float g_dy = 0.0f;
     auto issue_loads = [&](const int sb, const int h) {
         const uint8_t * blk = wrow + (size_t) sb * BYTES;
-        if constexpr (!Q6) {
+        if constexpr (NIB) {
             g_hdr = *(const uint4 *) blk;
             g_q = *(const uint4 *) (blk + (QT == 5 ? 48 : 16) + 64 * h + 16 * aq);
             if constexpr (QT == 5) g_qh = *(const uint4 *) (blk + 16 + 16 * (aq & 1));
+        } else if constexpr (Q2) {
+            // half h of a Q2_K block: qs[32h .. 32h+31] hold its 128 values as four 2-bit planes; this thread owns l = 8*aq .. 8*aq+7.  Blocks are 4-byte aligned.
+            g_hdr = make_uint4(ld32_a2(blk), ld32_a2(blk + 4), ld32_a2(blk + 8), ld32_a2(blk + 12));  // scales[16]: scale | min << 4
+            g6_ql0 = ld32_a2(blk + 16 + 32 * h + 8 * aq);
+            g6_ql1 = ld32_a2(blk + 16 + 32 * h + 8 * aq + 4);
+            g6_sc0 = ld32_a2(blk + 80);  // d | dmin << 16
+        } else if constexpr (Q3) {
+            // half h of a Q3_K block: qs[32h .. 32h+31] (planes as Q2_K), bit 4h + plane of hmask[l]; 2-byte aligned blocks
+            g6_ql0 = ld32_a2(blk + 32 + 32 * h + 8 * aq);
+            g6_ql1 = ld32_a2(blk + 32 + 32 * h + 8 * aq + 4);
+            g6_qh0 = ld32_a2(blk + 8 * aq);
+            g6_qh1 = ld32_a2(blk + 8 * aq + 4);
+            g6_sc0 = ld32_a2(blk + 96);
+            g6_sc1 = ld32_a2(blk + 100);
+            g6_ql2 = ld32_a2(blk + 104);
+            g6_d = ld16(blk + 108);
         } else {
             // half h of a Q6_K block: ql[64h .. 64h+63], qh[32h .. 32h+31], scales[8h .. 8h+7]; this thread owns l = 8*aq .. 8*aq+7
             g6_ql0 = ld32_a2(blk + 64 * h + 8 * aq);
@@ -149,7 +167,7 @@ __global__ void __launch_bounds__(BN * 4, BN == 64 ? (BM == 32 ? 3 : 2) : 1) k_m
             g_b3 = *(const uint4 *) (bsrc3 + bo);
         }
         if (h == 1 && tid < BM) {
-            if constexpr (!Q6) {
+            if constexpr (!NOMIN) {
                 g_bs0 = *(const uint4 *) mcol[sb].bsums;
                 g_bs1 = *(const uint4 *) (mcol[sb].bsums + 8);
             }
@@ -159,7 +177,45 @@ __global__ void __launch_bounds__(BN * 4, BN == 64 ? (BM == 32 ? 3 : 2) : 1) k_m
 
     auto stage = [&](const int h) {
         char * buf = smem + h * STAGE;
-        if constexpr (!Q6) {
+        if constexpr (Q2) {
+            // Q2_K: ONE piece, sc * level in 0 .. 45.  This thread: l = 8*aq .. +7 of the four planes w -> elements 32*w + l of the half, scale 2*w + (aq >> 1)
+            const int is = aq >> 1;
+            const uint32_t s0 = h ? g_hdr.z : g_hdr.x, s1 = h ? g_hdr.w : g_hdr.y;  // scales 8h .. 8h+3, 8h+4 .. 8h+7
+#pragma unroll
+            for (int w = 0; w < 4; ++w) {
+                const uint32_t scp = ((((w & 2) ? s1 : s0) >> (8 * (2 * (w & 1) + is))) & 0xFu) * 0x00010001u;
+                const int off = sw_off(arow, 2 * w + is) + 8 * (aq & 1);
+                // (byte products < 256: no carry crosses the bytes of a 16-bit lane)
+                *(uint2 *) (buf + off) = make_uint2(pk_mul_u16x2((g6_ql0 >> (2 * w)) & 0x03030303u, scp), pk_mul_u16x2((g6_ql1 >> (2 * w)) & 0x03030303u, scp));
+            }
+        } else if constexpr (Q3) {
+            // Q3_K: s * level with s = sc - 32 in -32 .. 31 and level = low2 - 4 * [hmask bit clear] in -4 .. 3 reaches +128 (-4 * -32), so the level is
+            // split, not folded into bsums (which bits are clear is not a sub-block constant): piece 0 = s * low2 in -96 .. 93, piece 1 = -s where the bit is
+            // clear, else 0, in -31 .. 32; s * level = piece 0 + 4 * piece 1 — two int8 pieces, exactly the CPU's integers.
+            typedef short short2v __attribute__((ext_vector_type(2)));
+            const int is = aq >> 1;
+            const uint32_t s03 = ((g6_sc0 >> (4 * h)) & 0x0F0F0F0Fu) | (((g6_ql2 >> (4 * h)) & 0x03030303u) << 4);      // six-bit scales 8h .. 8h+3
+            const uint32_t s47 = ((g6_sc1 >> (4 * h)) & 0x0F0F0F0Fu) | (((g6_ql2 >> (4 * h + 2)) & 0x03030303u) << 4);  // 8h+4 .. 8h+7
+#pragma unroll
+            for (int w = 0; w < 4; ++w) {
+                const int sc = (int) ((((w & 2) ? s47 : s03) >> (8 * (2 * (w & 1) + is))) & 0xFFu) - 32;
+                const uint32_t scp = ((uint32_t) sc & 0xFFFFu) * 0x00010001u;
+                const uint32_t nsb = ((uint32_t) (-sc) & 0xFFu) * 0x01010101u;
+                uint32_t o0[2], o1[2];
+#pragma unroll
+                for (int i = 0; i < 2; ++i) {
+                    const uint32_t u = ((i ? g6_ql1 : g6_ql0) >> (2 * w)) & 0x03030303u;
+                    const uint32_t hb = ((i ? g6_qh1 : g6_qh0) >> (4 * h + w)) & 0x01010101u;
+                    const short2v pa = __builtin_bit_cast(short2v, __builtin_amdgcn_perm(0u, u, 0x0c010c00u)) * __builtin_bit_cast(short2v, scp);
+                    const short2v pb = __builtin_bit_cast(short2v, __builtin_amdgcn_perm(0u, u, 0x0c030c02u)) * __builtin_bit_cast(short2v, scp);
+                    o0[i] = __builtin_amdgcn_perm(__builtin_bit_cast(uint32_t, pb), __builtin_bit_cast(uint32_t, pa), 0x06040200u);
+                    o1[i] = ((0x01010101u - hb) * 0xFFu) & nsb;
+                }
+                const int off = sw_off(arow, 2 * w + is) + 8 * (aq & 1);
+                *(uint2 *) (buf + off) = make_uint2(o0[0], o0[1]);
+                *(uint2 *) (buf + TA + off) = make_uint2(o1[0], o1[1]);
+            }
+        } else if constexpr (NIB) {
         // ---- weight pieces: this thread owns 16 values of sub-block 2*j2 (low nibbles) and of 2*j2+1 (high nibbles)
         const int j2 = 2 * h + (aq >> 1);
         uint32_t scp;  // (sc of sub-block 2*j2) | (sc of 2*j2+1) << 8
@@ -237,11 +293,26 @@ __global__ void __launch_bounds__(BN * 4, BN == 64 ? (BM == 32 ? 3 : 2) : 1) k_m
         }
         // ---- per-super-block metadata (staged with the second half; consumed at the end of that trip)
         if (h == 1) {
-            if constexpr (Q6) {
+            if constexpr (NOMIN) {
                 if (aq == 0) dd[arow] = make_float2(h2f(g6_d), 0.0f);
                 if (tid < BM) dyv[tid] = g_dy;
             }
-            if (!Q6 && aq == 0) {
+            if (Q2 && aq == 0) {
+                dd[arow] = make_float2(h2f((uint16_t) (g6_sc0 & 0xFFFF)), h2f((uint16_t) (g6_sc0 >> 16)));
+                uint32_t pm[8];
+#pragma unroll
+                for (int k = 0; k < 8; ++k) {  // mins 2k, 2k+1 (the high nibbles of scales[2k], [2k+1]) into the two 16-bit lanes, then 0x6400 | n == 1024 + n in f16
+                    typedef _Float16 half2m __attribute__((ext_vector_type(2)));
+                    const uint32_t mq = ((k < 2 ? g_hdr.x : (k < 4 ? g_hdr.y : (k < 6 ? g_hdr.z : g_hdr.w))) >> 4) & 0x0F0F0F0Fu;
+                    half2m a2 = __builtin_bit_cast(half2m, __builtin_amdgcn_perm(0u, mq, (k & 1) ? 0x0c030c02u : 0x0c010c00u) | 0x64006400u);
+                    a2 = a2 - (half2m){(_Float16) 1024.0f, (_Float16) 1024.0f};
+                    pm[k] = __builtin_bit_cast(uint32_t, a2);
+                }
+                uint4 * dm = (uint4 *) (Am + arow * MI_MS);
+                dm[0] = make_uint4(pm[0], pm[1], pm[2], pm[3]);
+                dm[1] = make_uint4(pm[4], pm[5], pm[6], pm[7]);
+            }
+            if (NIB && aq == 0) {
                 const float d = h2f((uint16_t) (g_hdr.x & 0xFFFF)), dmin = h2f((uint16_t) (g_hdr.x >> 16));
                 dd[arow] = make_float2(d, dmin);
                 const uint32_t hz = g_hdr.z, hw = g_hdr.w;
@@ -262,7 +333,7 @@ __global__ void __launch_bounds__(BN * 4, BN == 64 ? (BM == 32 ? 3 : 2) : 1) k_m
                 dm[0] = make_uint4(pm[0], pm[1], pm[2], pm[3]);
                 dm[1] = make_uint4(pm[4], pm[5], pm[6], pm[7]);
             }
-            if (!Q6 && tid < BM) {
+            if (!NOMIN && tid < BM) {
                 dyv[tid] = g_dy;
                 uint4 * dbm = (uint4 *) (Bm + tid * MI_MS);  // the Q8_K bsums are stored as f16 already
                 dbm[0] = g_bs0;
@@ -299,11 +370,11 @@ __global__ void __launch_bounds__(BN * 4, BN == 64 ? (BM == 32 ? 3 : 2) : 1) k_m
     auto fold = [&]() {
         typedef float float2v __attribute__((ext_vector_type(2)));
         half8 fam;
-        if constexpr (!Q6) fam = *(const half8 *) (Am + (nslab * 32 + fr) * MI_MS + kg * 16);
+        if constexpr (!NOMIN) fam = *(const half8 *) (Am + (nslab * 32 + fr) * MI_MS + kg * 16);
 #pragma unroll
         for (int t = 0; t < NTT; ++t) {
             float16v am = zerof;
-            if constexpr (!Q6) {
+            if constexpr (!NOMIN) {
                 if (KG == 1 || mhalf == 0) {  // the mins term belongs to the super-block, not to a K step: one wave group adds it
                     const half8 fbm = *(const half8 *) (Bm + (cb + t * 32 + fr) * MI_MS + kg * 16);
                     am = __builtin_amdgcn_mfma_f32_32x32x16_f16(fam, fbm, zerof, 0, 0, 0);
@@ -316,18 +387,20 @@ __global__ void __launch_bounds__(BN * 4, BN == 64 ? (BM == 32 ? 3 : 2) : 1) k_m
                 const int i = nslab * 32 + (r & 3) + 8 * (r >> 2) + 4 * kg;  // rows i, i + 1
                 const float4 sd = *(const float4 *) &dd[i];                   // (d, dmin) of both
                 int is0, is1;
-                if constexpr (QT == 4) { is0 = (acc[0][t][r] << 3) + acc[1][t][r]; is1 = (acc[0][t][r + 1] << 3) + acc[1][t][r + 1]; }
+                if constexpr (Q2) { is0 = acc[0][t][r]; is1 = acc[0][t][r + 1]; }
+                else if constexpr (Q3) { is0 = acc[0][t][r] + 4 * acc[1][t][r]; is1 = acc[0][t][r + 1] + 4 * acc[1][t][r + 1]; }
+                else if constexpr (QT == 4) { is0 = (acc[0][t][r] << 3) + acc[1][t][r]; is1 = (acc[0][t][r + 1] << 3) + acc[1][t][r + 1]; }
                 else if constexpr (QT == 5) {
                     is0 = (acc[0][t][r] << 4) + (acc[1][t][r] << 2) + acc[2][t][r];
                     is1 = (acc[0][t][r + 1] << 4) + (acc[1][t][r + 1] << 2) + acc[2][t][r + 1];
                 } else { is0 = (acc[0][t][r] << 6) + acc[1][t][r]; is1 = (acc[0][t][r + 1] << 6) + acc[1][t][r + 1]; }
 #if MMQ_FOLD_PACKED
                 float2v v = (float2v){(float) is0, (float) is1} * (float2v){sd.x, sd.z};
-                if constexpr (!Q6) v = __builtin_elementwise_fma(-(float2v){sd.y, sd.w}, (float2v){am[r], am[r + 1]}, v);
+                if constexpr (!NOMIN) v = __builtin_elementwise_fma(-(float2v){sd.y, sd.w}, (float2v){am[r], am[r + 1]}, v);
                 const float2v c = __builtin_elementwise_fma(dy2, v, (float2v){C[t][r], C[t][r + 1]});
 #else
                 float v0 = sd.x * (float) is0, v1 = sd.z * (float) is1;
-                if constexpr (!Q6) { v0 = __builtin_fmaf(-sd.y, am[r], v0); v1 = __builtin_fmaf(-sd.w, am[r + 1], v1); }
+                if constexpr (!NOMIN) { v0 = __builtin_fmaf(-sd.y, am[r], v0); v1 = __builtin_fmaf(-sd.w, am[r + 1], v1); }
                 const float2v c = {__builtin_fmaf(dy, v0, C[t][r]), __builtin_fmaf(dy, v1, C[t][r + 1])};
                 (void) dy2;
 #endif
@@ -403,11 +476,13 @@ __global__ void __launch_bounds__(BN * 4, BN == 64 ? (BM == 32 ? 3 : 2) : 1) k_m
 
 bool mmq_i8_supported(int type, int64_t K, int64_t N, int64_t M) {
     (void) N;
+    // (Q2_K / Q3_K: the tiled form only, from the 9 columns the mat-vec passes end at — graph.cpp: mmq_min_cols_for)
+    if (type == GGML_TYPE_Q2_K || type == GGML_TYPE_Q3_K) return (K % 256) == 0 && M >= 9;
     return (type == GGML_TYPE_Q4_K || type == GGML_TYPE_Q5_K || type == GGML_TYPE_Q6_K) && (K % 256) == 0 && M >= 2;
 }
 
 template <int QT, int BN, int BM = 128> static void launch_mmq8_t(hipStream_t s, mmq8_args a) {
-    constexpr int NP = QT == 5 ? 3 : 2;
+    constexpr int NP = QT == 5 ? 3 : (QT == 2 ? 1 : 2);
     const size_t lds = 2 * (size_t) (NP * BN * 128 + BM * 128) + (size_t) (BN + BM) * MI_MS + BN * sizeof(float2) + BM * sizeof(float);
     static std::atomic<uint32_t> lds_raised{0};  // one bit per device (common.h: ensure_dyn_lds)
     (void) ensure_dyn_lds((const void *) k_mmq_i8<QT, BN, BM>, lds, lds_raised);  // on failure the launch below fails and graph_compute reports it
@@ -581,7 +656,9 @@ int launch_mmq_i8_multi(hipStream_t s, int type, int n_mat, const mmq_mat_desc *
         if (bm == 32) launch_mmq8_t<QT, 64, 32>(s, a);   \
         else launch_mmq8_t<QT, 64, 64>(s, a);            \
     }
-        if (type == GGML_TYPE_Q4_K) MMQ_SKINNY(4) else if (type == GGML_TYPE_Q5_K) MMQ_SKINNY(5) else MMQ_SKINNY(6)
+        if (type == GGML_TYPE_Q4_K) MMQ_SKINNY(4) else if (type == GGML_TYPE_Q5_K) MMQ_SKINNY(5) else if (type == GGML_TYPE_Q6_K) MMQ_SKINNY(6)
+        else if (type == GGML_TYPE_Q2_K) MMQ_SKINNY(2) else if (type == GGML_TYPE_Q3_K) MMQ_SKINNY(3)
+        else { MI_ERR("launch_mmq_i8_multi: unsupported weight type %d", type); abort(); }
 #undef MMQ_SKINNY
     } else if (type == GGML_TYPE_Q4_K) {
         if (bn == 128) launch_mmq8_t<4, 128>(s, a);
@@ -589,9 +666,18 @@ int launch_mmq_i8_multi(hipStream_t s, int type, int n_mat, const mmq_mat_desc *
     } else if (type == GGML_TYPE_Q5_K) {
         if (bn == 128) launch_mmq8_t<5, 128>(s, a);
         else launch_mmq8_t<5, 64>(s, a);
-    } else {
+    } else if (type == GGML_TYPE_Q6_K) {
         if (bn == 128) launch_mmq8_t<6, 128>(s, a);
         else launch_mmq8_t<6, 64>(s, a);
+    } else if (type == GGML_TYPE_Q2_K) {
+        if (bn == 128) launch_mmq8_t<2, 128>(s, a);
+        else launch_mmq8_t<2, 64>(s, a);
+    } else if (type == GGML_TYPE_Q3_K) {
+        if (bn == 128) launch_mmq8_t<3, 128>(s, a);
+        else launch_mmq8_t<3, 64>(s, a);
+    } else {
+        MI_ERR("launch_mmq_i8_multi: unsupported weight type %d", type);
+        abort();
     }
     if (a.ksplit > 1 && reduce) launch_splitk_reduce_multi(s, a);  // (!reduce: the caller's next kernel sums the partials itself)
     return 0;

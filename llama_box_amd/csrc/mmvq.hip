@@ -526,7 +526,9 @@ template <typename T> static void launch_type(hipStream_t s, const mmvq_args & a
         }
         if (a0.fa_part) {
             if (glu || a0.norm_w || a0.fa_splits < 1 || a0.fa_splits > 16) { MI_ERR("launch_mmvq: bad attention-partials prologue request"); abort(); }
-            launch_stream<T, false, 3>(s, a0);
+            // (Q2_K / Q3_K: graph.cpp leaves the combine pass its own launch — the form is not built for them, no test model reaches it)
+            if constexpr (std::is_same<T, T_Q2K>::value || std::is_same<T, T_Q3K>::value) { MI_ERR("launch_mmvq: weight type %d has no attention-partials prologue", a0.type); abort(); }
+            else launch_stream<T, false, 3>(s, a0);
             return;
         }
         if (a0.norm_w) { if (glu) launch_stream<T, true, 2>(s, a0); else launch_stream<T, false, 2>(s, a0); }
@@ -603,6 +605,8 @@ int launch_mmvq_ss_count(const mmvq_args & a) {
 
 void launch_mmvq(hipStream_t s, const mmvq_args & a, int rows_per_wave) {
     switch (a.type) {
+        case GGML_TYPE_Q2_K: launch_type<T_Q2K>(s, a, rows_per_wave); break;
+        case GGML_TYPE_Q3_K: launch_type<T_Q3K>(s, a, rows_per_wave); break;
         case GGML_TYPE_Q4_K: launch_type<T_Q4K>(s, a, rows_per_wave); break;
         case GGML_TYPE_Q5_K: launch_type<T_Q5K>(s, a, rows_per_wave); break;
         case GGML_TYPE_Q6_K: launch_type<T_Q6K>(s, a, rows_per_wave); break;

@@ -224,6 +224,105 @@ struct T_Q6K {
     }
 };
 
+// ------------------------------------------------------------------------------------------------ Q2_K, Q3_K
+// 16 sub-blocks of 16 values, Q6_K's structure, and Q6_K's lane mapping: 4 lanes per super-block, lane (n, t) owns l = 16t .. 16t+15 of half n — the 16
+// bytes qs[32n + 16t ..], whose four 2-bit planes j are the value groups 128n + 32j + 16t .. + 15, each exactly ONE sub-block (8n + 2j + t) and one aligned
+// 16-byte piece of the activation block.  So a lane's 64 values are one 16-byte load (Q3_K: a second one for the 16 hmask bytes of the same l), the header
+// loads are shared by the four lanes of a block through the cache, and K = 4096 is one trip of a wave as for the other K-quants.  (Two lanes of 128 values
+// would halve the waves that fit a row of K = 4096; eight would split a byte's four planes between lanes that then both fetch it.)  Q2_K blocks (84 bytes)
+// are 4-byte aligned, Q3_K blocks (110) 2-byte aligned: the loads carry the 2-byte type, which gfx950 serves as whole dwordx4 / dwordx2.
+// Levels meet the int8 activations in v_dot4_i32_i8; the sub-block scale multiplies the 16-value sum in int32 (|sum| <= 16 * 127 * 7, times 32: far inside
+// 24 bits); the Q2_K min term and the Q3_K "-4" of a clear hmask bit — taken as (low2 | hbit << 2) - 4 — come from the activation block's 16-value sums.
+// One f32 term per lane and super-block follows in the reference's expression: Q2_K (dy * d) * isum - (dy * dmin) * summs, Q3_K (d * dy) * isum.
+struct T_Q2K {
+    typedef q8k_dev act;
+    static constexpr int BLK = 256, BYTES = 84, PPB = 4;
+    struct raw { u128_a2 q; u64_a2 s; uint32_t dm; };  // s = scales[8n .. 8n+7], dm = d | dmin << 16
+    static constexpr int DW = 7;
+    static __device__ __forceinline__ raw load(const uint8_t * __restrict__ row, int p, int = 0) {
+        const uint8_t * blk = row + (size_t) (p >> 2) * BYTES;
+        const int n = (p >> 1) & 1, t = p & 1;
+        raw r;
+        r.q = ld_stream((const u128_a2 *) (blk + 16 + 32 * n + 16 * t));
+        r.s = ld_stream((const u64_a2 *) (blk + 8 * n));
+        r.dm = ld32_a2(blk + 80);
+        return r;
+    }
+    template <int NC> static __device__ __forceinline__ void dot(const raw & r, int p, const act * __restrict__ y, int nblk, float * acc) {
+        const int b = p >> 2, n = (p >> 1) & 1, t = p & 1;
+        const float d = h2f((uint16_t) (r.dm & 0xFFFFu)), dmin = h2f((uint16_t) (r.dm >> 16));
+        const uint32_t Q[4] = {r.q.x, r.q.y, r.q.z, r.q.w};
+        // plane j of this lane uses scale byte 2j + t of the half's eight
+        const uint32_t sb[4] = {(r.s.x >> (8 * t)) & 0xFFu, (r.s.x >> (8 * (t + 2))) & 0xFFu, (r.s.y >> (8 * t)) & 0xFFu, (r.s.y >> (8 * (t + 2))) & 0xFFu};
+#pragma unroll
+        for (int col = 0; col < NC; ++col) {
+            const act * yb = y + (size_t) col * nblk + b;
+            int isum = 0, msum = 0;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const uint4 yk = *(const uint4 *) (yb->qs + 128 * n + 32 * j + 16 * t);
+                int s = dot4((int) ((Q[0] >> (2 * j)) & 0x03030303u), (int) yk.x, 0);
+                s = dot4((int) ((Q[1] >> (2 * j)) & 0x03030303u), (int) yk.y, s);
+                s = dot4((int) ((Q[2] >> (2 * j)) & 0x03030303u), (int) yk.z, s);
+                s = dot4((int) ((Q[3] >> (2 * j)) & 0x03030303u), (int) yk.w, s);
+                const int ys = (int) h2f(yb->bsums[8 * n + 2 * j + t]);  // (an exact f16 integer)
+                isum += __mul24((int) (sb[j] & 0xFu), s);
+                msum += __mul24((int) (sb[j] >> 4), ys);
+            }
+            acc[col] += (yb->d * d) * (float) isum - (yb->d * dmin) * (float) msum;
+        }
+    }
+};
+struct T_Q3K {
+    typedef q8k_dev act;
+    static constexpr int BLK = 256, BYTES = 110, PPB = 4;
+    struct raw { u128_a2 q, h; uint32_t a0, a1, a2; uint16_t d; };
+    static constexpr int DW = 12;
+    static __device__ __forceinline__ raw load(const uint8_t * __restrict__ row, int p, int = 0) {
+        const uint8_t * blk = row + (size_t) (p >> 2) * BYTES;
+        const int n = (p >> 1) & 1, t = p & 1;
+        raw r;
+        r.h = ld_stream((const u128_a2 *) (blk + 16 * t));
+        r.q = ld_stream((const u128_a2 *) (blk + 32 + 32 * n + 16 * t));
+        r.a0 = ld32_a2(blk + 96);
+        r.a1 = ld32_a2(blk + 100);
+        r.a2 = ld32_a2(blk + 104);
+        r.d = ld16(blk + 108);
+        return r;
+    }
+    template <int NC> static __device__ __forceinline__ void dot(const raw & r, int p, const act * __restrict__ y, int nblk, float * acc) {
+        const int b = p >> 2, n = (p >> 1) & 1, t = p & 1;
+        const float d = h2f(r.d);
+        const uint32_t Q[4] = {r.q.x, r.q.y, r.q.z, r.q.w}, H[4] = {r.h.x, r.h.y, r.h.z, r.h.w};
+        // the six-bit scales 8n .. 8n+3 and 8n+4 .. 8n+7 as bytes of two dwords (low four bits from a0 / a1, upper two from a2)
+        const uint32_t s03 = ((r.a0 >> (4 * n)) & 0x0F0F0F0Fu) | (((r.a2 >> (4 * n)) & 0x03030303u) << 4);
+        const uint32_t s47 = ((r.a1 >> (4 * n)) & 0x0F0F0F0Fu) | (((r.a2 >> (4 * n + 2)) & 0x03030303u) << 4);
+        const int sc[4] = {(int) ((s03 >> (8 * t)) & 0xFFu) - 32, (int) ((s03 >> (8 * (t + 2))) & 0xFFu) - 32,
+                           (int) ((s47 >> (8 * t)) & 0xFFu) - 32, (int) ((s47 >> (8 * (t + 2))) & 0xFFu) - 32};
+        uint32_t v[4][4];  // low2 | hbit << 2 = level + 4
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) v[j][i] = ((Q[i] >> (2 * j)) & 0x03030303u) | (((H[i] >> (4 * n + j)) & 0x01010101u) << 2);
+#pragma unroll
+        for (int col = 0; col < NC; ++col) {
+            const act * yb = y + (size_t) col * nblk + b;
+            int isum = 0;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const uint4 yk = *(const uint4 *) (yb->qs + 128 * n + 32 * j + 16 * t);
+                int s = dot4((int) v[j][0], (int) yk.x, 0);
+                s = dot4((int) v[j][1], (int) yk.y, s);
+                s = dot4((int) v[j][2], (int) yk.z, s);
+                s = dot4((int) v[j][3], (int) yk.w, s);
+                const int ys = (int) h2f(yb->bsums[8 * n + 2 * j + t]);
+                isum += __mul24(sc[j], s - 4 * ys);
+            }
+            acc[col] += (d * yb->d) * (float) isum;
+        }
+    }
+};
+
 // ------------------------------------------------------------------------------------------------ Q8_0
 struct T_Q80 {
     typedef q80_dev act;

@@ -369,6 +369,27 @@ __device__ __forceinline__ float dequant_elem(const int type, const uint8_t * __
             const float d = h2f(ld16(b + 208));
             return d * (float) sc[(l >> 4) + 2 * k] * (float) q;
         }
+        case GGML_TYPE_Q2_K: {
+            // {scales[16], qs[64], d, dmin}: value 128 n + 32 j + l is plane j of qs[32 n + l], sub-block 8 n + 2 j + l / 16; y = (d * sc) * level - dmin * m
+            const uint8_t * b = row + (i >> 8) * 84;
+            const int e = (int) (i & 255), n = e >> 7, j = (e >> 5) & 3, l = e & 31;
+            const int s = b[8 * n + 2 * j + (l >> 4)];
+            const int q = (b[16 + 32 * n + l] >> (2 * j)) & 3;
+            const float dl = h2f(ld16(b + 80)) * (float) (s & 0xF), ml = h2f(ld16(b + 82)) * (float) (s >> 4);
+            return dl * (float) q - ml;
+        }
+        case GGML_TYPE_Q3_K: {
+            // {hmask[32], qs[64], scales[12], d}: planes as Q2_K; a CLEAR bit 4 n + j of hmask[l] subtracts 4; six-bit scales used as sc - 32; y = (d * (sc - 32)) * level
+            const uint8_t * b = row + (i >> 8) * 110;
+            const int e = (int) (i & 255), n = e >> 7, j = (e >> 5) & 3, l = e & 31;
+            const int is = 8 * n + 2 * j + (l >> 4);
+            const uint8_t * sc = b + 96;
+            const int lo4 = is < 8 ? (sc[is] & 0xF) : (sc[is - 8] >> 4);
+            const int s = (lo4 | (((sc[8 + (is & 3)] >> (2 * (is >> 2))) & 3) << 4)) - 32;
+            const int q = (int) ((b[32 + 32 * n + l] >> (2 * j)) & 3) - (((b[l] >> (4 * n + j)) & 1) ? 0 : 4);
+            const float dl = h2f(ld16(b + 108)) * (float) s;
+            return dl * (float) q;
+        }
         case GGML_TYPE_Q4_0: case GGML_TYPE_Q4_1: case GGML_TYPE_Q5_0: case GGML_TYPE_Q5_1: case GGML_TYPE_IQ4_NL: {
             // dequantize_row_* through the octet helpers the KV cache in these formats is read with (kv_dequant.h): level * d (+ m), one rounding an operation
             const char * b = (const char *) row + (i >> 5) * kv_block_bytes_any(type);

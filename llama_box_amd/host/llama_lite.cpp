@@ -129,6 +129,37 @@ static void synth_block(ggml_type type, uint64_t key, int64_t K, float wscale, u
             if (one) { memcpy(p, &hm, 2); p += 2; }
             fill(p, five ? 20 : 16);
         } break;
+        case GGML_TYPE_Q2_K: {
+            // {scales[16], qs[64], d, dmin}: levels uniform in 0 .. 3 (mean 1.5), 4-bit scales in 4 .. 15 with the min tied to the scale (m = sc +- 1) and
+            // dmin = 1.5 d, so that d sc level - dmin m is ~zero-mean; std ~ d * rms(sc) * std(level) = d * 10 * 1.12
+            block_q2_K * b = (block_q2_K *) out;
+            uint64_t r = splitmix64(s), r2 = splitmix64(s);
+            for (int j = 0; j < 16; ++j) {
+                const int sc = 4 + (int) ((r >> (4 * j)) & 0xF) % 12;
+                const int m = std::min(15, std::max(0, sc + (int) ((r2 >> (4 * j)) & 0xF) % 3 - 1));
+                b->scales[j] = (uint8_t) (sc | (m << 4));
+            }
+            fill(b->qs, 64);
+            const float d = scale * rk / 11.2f;
+            b->d = f32_to_f16(d);
+            b->dmin = f32_to_f16(1.5f * d);
+        } break;
+        case GGML_TYPE_Q3_K: {
+            // {hmask[32], qs[64], scales[12], d}: levels uniform in -4 .. 3 (rms 2.35), six-bit scales 32 +- (8 .. 31) — the sign of sc - 32 random, as
+            // Q6_K's int8 scales above — so the values are ~zero-mean; std ~ d * rms(sc - 32) * rms(level) = d * 20.7 * 2.35
+            block_q3_K * b = (block_q3_K *) out;
+            fill(b->hmask, 32 + 64);
+            uint64_t r = splitmix64(s), r2 = splitmix64(s);
+            int L[16];
+            for (int j = 0; j < 16; ++j) {
+                const uint64_t rr = j < 8 ? r : r2;
+                const int v = 8 + (int) ((rr >> (8 * (j & 7))) & 0x7F) % 24;  // 8 .. 31
+                L[j] = ((rr >> (8 * (j & 7) + 7)) & 1) ? 32 - v : 32 + v;
+            }
+            for (int j = 0; j < 8; ++j) b->scales[j] = (uint8_t) ((L[j] & 0xF) | ((L[j + 8] & 0xF) << 4));
+            for (int k = 0; k < 4; ++k) b->scales[8 + k] = (uint8_t) ((L[k] >> 4) | ((L[k + 4] >> 4) << 2) | ((L[k + 8] >> 4) << 4) | ((L[k + 12] >> 4) << 6));
+            b->d = f32_to_f16(scale * rk / 48.5f);
+        } break;
         default: LLM_ASSERT(!"synth_block: unsupported type");
     }
 }
@@ -194,6 +225,24 @@ static void block_values(ggml_type type, const uint8_t * p, float * y) {
                     y[128 * n + l + 64] = d * (float) sc[is + 4] * (float) q3;
                     y[128 * n + l + 96] = d * (float) sc[is + 6] * (float) q4;
                 }
+            }
+        } break;
+        case GGML_TYPE_Q2_K: {
+            const block_q2_K * b = (const block_q2_K *) p;
+            const float d = f16_to_f32(b->d), dmin = f16_to_f32(b->dmin);
+            for (int i = 0; i < 256; ++i) {
+                const int n = i >> 7, j = (i >> 5) & 3, l = i & 31, sm = b->scales[8 * n + 2 * j + l / 16];
+                y[i] = d * (float) (sm & 0xF) * (float) ((b->qs[32 * n + l] >> (2 * j)) & 3) - dmin * (float) (sm >> 4);
+            }
+        } break;
+        case GGML_TYPE_Q3_K: {
+            const block_q3_K * b = (const block_q3_K *) p;
+            const float d = f16_to_f32(b->d);
+            for (int i = 0; i < 256; ++i) {
+                const int n = i >> 7, j = (i >> 5) & 3, l = i & 31, is = 8 * n + 2 * j + l / 16;
+                const int sc = ((is < 8 ? b->scales[is] & 0xF : b->scales[is - 8] >> 4) | (((b->scales[8 + (is & 3)] >> (2 * (is >> 2))) & 3) << 4)) - 32;
+                const int q = (int) ((b->qs[32 * n + l] >> (2 * j)) & 3) - (((b->hmask[l] >> (4 * n + j)) & 1) ? 0 : 4);
+                y[i] = d * (float) sc * (float) q;
             }
         } break;
         case GGML_TYPE_Q4_0: case GGML_TYPE_Q4_1: case GGML_TYPE_Q5_0: case GGML_TYPE_Q5_1: case GGML_TYPE_IQ4_NL: {  // the 32 values of one block
@@ -349,6 +398,9 @@ extern "C" int llm_preset(const char * name, struct llm_hparams * hp) {
     else if (n == "test-llama-legacy") set("llama", 3, 256, 4, 2, 64, 512, 512, 512, 10000.0f, 1e-5f, 0, 0, LLM_FTYPE_MIXED_LEGACY);
     else if (n == "test-qwen2-legacy") set("qwen2", 2, 256, 4, 2, 64, 768, 768, 512, 1000000.0f, 1e-6f, GGML_ROPE_TYPE_NEOX, 1, LLM_FTYPE_MIXED_LEGACY);
     else if (n == "llama2-7b-q4_0") set("llama", 32, 4096, 32, 32, 128, 11008, 32000, 4096, 10000.0f, 1e-5f, 0, 0, LLM_FTYPE_Q4_0);
+    else if (n == "test-llama-kq23") set("llama", 3, 256, 4, 2, 64, 512, 512, 512, 10000.0f, 1e-5f, 0, 0, LLM_FTYPE_MIXED_KQ23);
+    else if (n == "llama3-8b-q3_k_m") set("llama", 32, 4096, 32, 8, 128, 14336, 128256, 8192, 500000.0f, 1e-5f, 0, 0, LLM_FTYPE_Q3_K_M);
+    else if (n == "llama3-70b-q2_k") set("llama", 80, 8192, 64, 8, 128, 28672, 128256, 8192, 500000.0f, 1e-5f, 0, 0, LLM_FTYPE_Q2_K);
     else if (n == "test-qwen2") set("qwen2", 2, 256, 4, 2, 64, 768, 768, 512, 1000000.0f, 1e-6f, GGML_ROPE_TYPE_NEOX, 1, LLM_FTYPE_MIXED);
     else return -1;
     return 0;
@@ -424,6 +476,25 @@ static ggml_type pick_type(const llm_hparams & hp, const char * what, int il) {
             unsigned h = (unsigned) il * 7u;
             for (char c : w) h = h * 31u + (unsigned char) c;
             return cyc[h % 6];
+        }
+        // the two smallest K-quant mixes, recalled from llama.cpp's quantiser (not verified against it): what matters here is that Q2_K and Q3_K meet each
+        // other and the larger K-quants inside one layer
+        case LLM_FTYPE_Q3_K_M:
+            if (w == "output") return GGML_TYPE_Q6_K;
+            if (w == "attn_output") return GGML_TYPE_Q4_K;
+            if (w == "attn_v") return more ? GGML_TYPE_Q5_K : GGML_TYPE_Q4_K;
+            if (w == "ffn_down") return more ? GGML_TYPE_Q5_K : GGML_TYPE_Q4_K;
+            return GGML_TYPE_Q3_K;
+        case LLM_FTYPE_Q2_K:
+            if (w == "output") return GGML_TYPE_Q6_K;
+            if (w == "attn_v" || w == "attn_output" || w == "ffn_down") return GGML_TYPE_Q3_K;
+            return GGML_TYPE_Q2_K;
+        case LLM_FTYPE_Q3_K_S: return w == "output" ? GGML_TYPE_Q6_K : GGML_TYPE_Q3_K;
+        case LLM_FTYPE_MIXED_KQ23: {
+            static const ggml_type cyc[4] = {GGML_TYPE_Q3_K, GGML_TYPE_Q2_K, GGML_TYPE_Q4_K, GGML_TYPE_Q6_K};
+            unsigned h = (unsigned) il * 7u;
+            for (char c : w) h = h * 31u + (unsigned char) c;
+            return cyc[h % 4];
         }
         default: return GGML_TYPE_Q8_0;
     }

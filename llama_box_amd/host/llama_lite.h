@@ -32,6 +32,11 @@ enum llm_ftype {
     LLM_FTYPE_Q5_1 = 9,
     LLM_FTYPE_IQ4_NL = 10,
     LLM_FTYPE_MIXED_LEGACY = 11, /* test recipe: cycles Q4_0/Q4_1/Q5_0/Q5_1/IQ4_NL/Q8_0 over the tensors of one tiny model */
+    /* the two smallest K-quants (the mixes are recalled from llama.cpp's quantiser, not verified against it) */
+    LLM_FTYPE_Q3_K_M = 12,       /* Q3_K base; attn_output Q4_K; attn_v and ffn_down Q4_K, Q5_K in the "more bits" layers; output Q6_K */
+    LLM_FTYPE_Q2_K = 13,         /* Q2_K base; attn_v, attn_output, ffn_down Q3_K; output Q6_K */
+    LLM_FTYPE_Q3_K_S = 14,       /* everything Q3_K, output Q6_K */
+    LLM_FTYPE_MIXED_KQ23 = 15,   /* test recipe: cycles Q3_K/Q2_K/Q4_K/Q6_K over the tensors of one tiny model */
 };
 
 struct llm_hparams {

@@ -157,6 +157,8 @@ int main(void) {
     OFF(struct ggml_backend_event, device);
     OFF(struct ggml_backend_event, context);
     SZ(block_q8_0); OFF(block_q8_0, d); OFF(block_q8_0, qs);
+    SZ(block_q2_K); OFF(block_q2_K, scales); OFF(block_q2_K, qs); OFF(block_q2_K, d); OFF(block_q2_K, dmin);
+    SZ(block_q3_K); OFF(block_q3_K, hmask); OFF(block_q3_K, qs); OFF(block_q3_K, scales); OFF(block_q3_K, d);
     SZ(block_q4_K); OFF(block_q4_K, scales); OFF(block_q4_K, qs);
     SZ(block_q5_K); OFF(block_q5_K, scales); OFF(block_q5_K, qh); OFF(block_q5_K, qs);
     SZ(block_q6_K); OFF(block_q6_K, ql); OFF(block_q6_K, qh); OFF(block_q6_K, scales); OFF(block_q6_K, d);
