@@ -735,6 +735,10 @@ static ggml_backend_t dev_init_backend(ggml_backend_dev_t dev, const char *) {
     if (const char * e = getenv("GGML_MI355X_MMQ_I8")) c->opt.mmq_i8 = atoi(e) != 0;
     if (const char * e = getenv("GGML_MI355X_MM_MERGE")) c->opt.mm_merge = atoi(e) != 0;
     if (const char * e = getenv("GGML_MI355X_MMQ_BN")) c->opt.mmq_bn = atoi(e);
+    if (const char * e = getenv("GGML_MI355X_BF16_NT")) c->opt.bf16_nt = atoi(e) != 0;
+    if (const char * e = getenv("GGML_MI355X_BF16_FORM")) c->opt.bf16_form = atoi(e);
+    if (const char * e = getenv("GGML_MI355X_BF16_PREROUND")) c->opt.bf16_preround = atoi(e) != 0;
+    if (const char * e = getenv("GGML_MI355X_BF16_MMV_MAX_COLS")) c->opt.bf16_mmv_max_cols = atoi(e);
     if (const char * e = getenv("GGML_MI355X_MMQ_SKINNY")) c->opt.mmq_skinny = atoi(e) != 0;
     if (const char * e = getenv("GGML_MI355X_SKINNY_ROPE")) c->opt.skinny_rope = atoi(e) != 0;
     if (const char * e = getenv("GGML_MI355X_SKINNY_MIX")) c->opt.skinny_mix = atoi(e) != 0;
@@ -848,6 +852,10 @@ static int api_set_option(ggml_backend_t be, const char * key, const char * valu
     else if (k == "mmq_i8") c->opt.mmq_i8 = v != 0;
     else if (k == "mm_merge") c->opt.mm_merge = v != 0;
     else if (k == "mmq_bn") c->opt.mmq_bn = v;
+    else if (k == "bf16_form") c->opt.bf16_form = v;
+    else if (k == "bf16_mmv_max_cols") c->opt.bf16_mmv_max_cols = v;
+    else if (k == "bf16_nt") c->opt.bf16_nt = v != 0;
+    else if (k == "bf16_preround") c->opt.bf16_preround = v != 0;
     else if (k == "mmq_skinny") c->opt.mmq_skinny = v != 0;
     else if (k == "skinny_rope") c->opt.skinny_rope = v != 0;
     else if (k == "skinny_mix") c->opt.skinny_mix = v != 0;

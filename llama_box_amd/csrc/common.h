@@ -114,6 +114,9 @@ static_assert(sizeof(q81_dev) == 40, "q81_dev");
 
 struct backend_ctx;
 
+#define MI_BF16_MMV_MAX_COLS 8  // default hand-over from the bf16 streaming kernel's multi-column form to the 16 x 16 tiles (option bf16_mmv_max_cols)
+#define MI_BF16_NT 1            // default load policy of the bf16 streaming kernel: non-temporal (option bf16_nt / GGML_MI355X_BF16_NT)
+#define MI_BF16_PREROUND 1      // default of option bf16_preround: on (measured 1.25 - 1.45 x faster at 512 and 2048 columns: profiles/r09_bf16_bench.txt)
 struct options {
     bool graphs = true;        // hipGraph capture + replay of repeated graphs
     bool fusion = true;        // node fusion (norm+mul, mul_mat+add, ...)
@@ -134,6 +137,11 @@ struct options {
     bool skinny_mix = true;    // -np decode steps: sibling mat-muls stored in two K-quant formats (Q4_K wq / wk + Q6_K wv) share one skinny launch
     bool mmq_skinny = true;    // 2..32 columns: weight-streaming matrix-core kernel (mmq_skinny.hip) instead of the tiled GEMM
     int mmq_bn = 0;            // force the weight-panel height of mmq_i8 (64 / 128); 0 = pick by grid size
+    // bf16 weight matrices (mmbf.hip)
+    int bf16_form = -1;        // -1: routed; MI_BF16_DOT .. MI_BF16_MMA: that form wherever it can serve the operands (measurements and tests)
+    int bf16_mmv_max_cols = MI_BF16_MMV_MAX_COLS;  // widest batch on the streaming kernel; wider ones go to the matrix cores
+    int bf16_nt = MI_BF16_NT;  // non-temporal weight loads in the streaming kernel
+    int bf16_preround = MI_BF16_PREROUND;  // batches on the 32 x 32 tiles: src1 rounded to bf16 once into scratch instead of in every workgroup's loop
     int fa_splits = 0;         // 0 = auto
     bool fa_wo = false;        // decode: attention as few fat splits whose merge is the wo mat-vec's prologue (no combine launch).  Correct and
                                // tested, OFF by default: a KV trip of the lane-parallel kernel is a ~4 us dependent chain, so 9 splits of 2

@@ -62,7 +62,7 @@ static bool mm_cache_image_ok(const ggml_tensor * op) {
     if (!(kv_type_is_block(a->type) || a->type == GGML_TYPE_BF16 || a->type == GGML_TYPE_Q8_0)) return false;
     // a VIEW into a cache (or a batch of matrices), never a plain 2-D weight: llama.cpp's loader probes every weight type with a plain tensor, and a model stored
     // in q4_0 / q5_1 / bf16 ... must get the same answer there as at graph time — a q4_0 ... iq4_nl matrix goes to the quantised mat-vec / mat-mul kernels
-    // (supports_op below), a bf16 one stays on the CPU backend; neither takes an image of a whole weight matrix per step
+    // (supports_op below), a bf16 one to the bf16 kernels of mmbf.hip (bf16_weight_ok); neither takes an image of a whole weight matrix per step
     if (a->view_src == nullptr && a->ne[2] == 1) return false;
     // ... nor a view of one: a 2-D view of a weight in Q8_0 or a 4- / 5-bit block format keeps the quantised mat-vec / mat-mul kernels (the integer-dot
     // arithmetic of the reference)
@@ -108,14 +108,24 @@ static int fa_route(const ggml_tensor * op) {
     return (k16 && v16) ? 1 : 3;
 }
 
-// MUL_MAT_ID (mmid.hip): `as` [K, N, n_expert] in a mat-vec format, f16 or f32 with contiguous rows; b f32 [K, n_used | 1, n_tokens]; ids I32 [n_used, n_tokens],
+// MUL_MAT whose src0 is a bf16 WEIGHT (mmbf.hip): one matrix with contiguous rows — a plain tensor (what llama.cpp's loader probes with) or a 2-D view rooted in a
+// weights buffer; any K and any alignment (what is not 16-byte aligned or has K % 8 != 0 takes the dot kernel's scalar path).  Asked AFTER mm_cache_image_ok: a bf16
+// KV-cache view keeps its f16 image.  Split (-sm row) and row-parallel buffer types keep refusing the format.
+static bool bf16_weight_ok(const ggml_tensor * a) {
+    if (a->type != GGML_TYPE_BF16 || a->ne[2] != 1 || a->ne[3] != 1 || a->nb[0] != 2) return false;
+    const ggml_backend_buffer_t root = a->view_src && a->view_src->buffer ? a->view_src->buffer : a->buffer;
+    if (a->view_src && !(root && root->usage == GGML_BACKEND_BUFFER_USAGE_WEIGHTS)) return false;
+    return !buffer_is_rowpar(root) && !buffer_is_split(a->buffer);
+}
+
+// MUL_MAT_ID (mmid.hip): `as` [K, N, n_expert] in a mat-vec format, f16, bf16 or f32 with contiguous rows; b f32 [K, n_used | 1, n_tokens]; ids I32 [n_used, n_tokens],
 // possibly a strided view (ggml_top_k); dst f32 [N, n_used, n_tokens].  Shapes, types and strides only.
 static bool mm_id_ok(const ggml_tensor * op) {
     const ggml_tensor * a = op->src[0];
     const ggml_tensor * b = op->src[1];
     const ggml_tensor * ids = op->src[2];
     if (!a || !b || !ids || b->type != GGML_TYPE_F32 || ids->type != GGML_TYPE_I32 || op->type != GGML_TYPE_F32 || !ggml_abi_is_contiguous(op)) return false;
-    if (!(is_quant(a->type) || a->type == GGML_TYPE_F16 || a->type == GGML_TYPE_F32) || !rows_contig(a) || a->ne[3] != 1 || a->ne[0] % ggml_abi_blck_size(a->type) != 0) return false;
+    if (!(is_quant(a->type) || a->type == GGML_TYPE_F16 || a->type == GGML_TYPE_BF16 || a->type == GGML_TYPE_F32) || !rows_contig(a) || a->ne[3] != 1 || a->ne[0] % ggml_abi_blck_size(a->type) != 0) return false;
     if ((is_l32_type(a->type) || is_kq23_type(a->type)) && !l32_layout_ok(a)) return false;
     if (buffer_is_rowpar(a->view_src ? a->view_src->buffer : a->buffer)) return false;  // (row-parallel weights hold a slice of every row: MUL_MAT only)
     if (b->ne[0] != a->ne[0] || b->nb[0] != 4 || b->ne[3] != 1 || (b->nb[1] % 4) || (b->nb[2] % 4)) return false;
@@ -149,6 +159,7 @@ bool supports_op(const ggml_tensor * op) {
                 return a->ne[2] == 1 && a->ne[3] == 1 && rows_contig(a) && b->nb[0] == 4 && a->ne[0] % ggml_abi_blck_size(a->type) == 0;
             }
             if (a->type == GGML_TYPE_F16 || a->type == GGML_TYPE_F32) return true;
+            if (a->type == GGML_TYPE_BF16) return bf16_weight_ok(a) && b->nb[0] == 4;
             return false;
         }
         case GGML_OP_MUL_MAT_ID:
@@ -187,7 +198,7 @@ bool supports_op(const ggml_tensor * op) {
         case GGML_OP_GET_ROWS:
             if ((is_l32_type(a->type) || is_kq23_type(a->type)) && !l32_layout_ok(a)) return false;  // (token_embd in q4_0 / q2_K / q3_K ...: the block alignment and buffer types of the MUL_MAT arm)
             return b->type == GGML_TYPE_I32 && op->type == GGML_TYPE_F32 && rows_contig(a) && op->nb[0] == 4 &&
-                   (is_quant(a->type) || a->type == GGML_TYPE_F16 || a->type == GGML_TYPE_F32);
+                   (is_quant(a->type) || a->type == GGML_TYPE_F16 || a->type == GGML_TYPE_BF16 || a->type == GGML_TYPE_F32);
         case GGML_OP_SET_ROWS:
             if (kv_store_type(op->type))  // a cache row in q4_0 / q4_1 / q5_0 / q5_1 / iq4_nl / bf16: the type's from_float per block of 32 (kv_types.hip)
                 return a->type == GGML_TYPE_F32 && b->type == GGML_TYPE_I64 && a->nb[0] == 4 && (a->ne[0] % 32) == 0 && (a->nb[1] % 16) == 0 && (a->nb[2] % 16) == 0 && (a->nb[3] % 16) == 0 &&
@@ -282,6 +293,10 @@ static ws_plan plan_ws(backend_ctx * c, const ggml_cgraph * g) {
             // (K.q of a prompt micro-batch on the non-flash path: statistics + partial records of the two-pass matrix-core form)
             if (c->opt.attn_nf && n->src[1]->type == GGML_TYPE_F32 && n->src[1]->ne[1] >= fattn_mma_min_q() && n->src[0]->ne[0] == 128 && n->src[1]->ne[3] == 1)
                 p.aux_bytes = std::max(p.aux_bytes, attn_nf_mma_ws_bytes(TD(n->src[1]), fattn_mma_pick_splits(TD(n->src[1]), TD(n->src[0]))));
+        } else if (n->op == GGML_OP_MUL_MAT && n->src[0]->type == GGML_TYPE_BF16) {
+            // a bf16 weight (mmbf.hip): the streaming mat-vec stages its columns in LDS and the tile forms add up in registers / LDS; only the 32 x 32 tiles with
+            // src1 rounded once (option bf16_preround) take scratch.  The activation area is not touched
+            if (c->opt.bf16_preround) p.aux_bytes = std::max(p.aux_bytes, mul_mat_bf16_workspace_bytes(TD(n->src[0]), TD(n->src[1])));
         } else if (n->op == GGML_OP_FLASH_ATTN_EXT) {
             const tdesc q = TD(n->src[0]), k = TD(n->src[1]), v = TD(n->src[2]);
             // (both forms a 33+-token batch may take — matrix-core tiles or, for a mask known to be sparse, position lists — fit this)
@@ -485,6 +500,7 @@ static const char * type_tag(int t) {
         case GGML_TYPE_Q5_0: return "q5_0";
         case GGML_TYPE_Q5_1: return "q5_1";
         case GGML_TYPE_IQ4_NL: return "iq4_nl";
+        case GGML_TYPE_BF16: return "bf16";
         default: return "f";
     }
 }
@@ -1814,6 +1830,19 @@ static int run_node(exec_state & st, int i) {
             }
             if (!is_quant(a->type) && fuse && c->opt.attn_nf && try_fuse_attn_nf(st, i)) return 1;
             if (!is_quant(a->type) && fuse && c->opt.attn_nf && try_fuse_attn_nf_mma(st, i)) return 1;
+            if (a->type == GGML_TYPE_BF16) {  // a bf16 weight: the form and its timing class are decided in mmbf.hip; no prologue, no activation cache; scratch only for src1 rounded once (option bf16_preround)
+                if (!bf16_weight_ok(a) || b->nb[0] != 4) {
+                    MI_ERR("graph_compute: node %d '%s': a bf16 src0 the backend does not serve (supports_op answers false for it)", i, n->name);
+                    return -1;
+                }
+                const tdesc ta = TD(a), tb = TD(b), tn = TD(n);
+                const int form = mul_mat_bf16_form(ta, tb, tn, c->opt.bf16_form, c->opt.bf16_mmv_max_cols), nl = mul_mat_bf16_launches(form, ta, tb);
+                timed_scope ts(c, mul_mat_bf16_class(form, b->ne[1]), (double) ggml_abi_nbytes(a) * nl);
+                const bool pre = form == MI_BF16_MMA && c->opt.bf16_preround && c->ws && mul_mat_bf16_workspace_bytes(ta, tb) > 0 && st.aux_off + mul_mat_bf16_workspace_bytes(ta, tb) <= c->ws_size;
+                launch_mul_mat_bf16(s, ta, tb, tn, form, c->opt.bf16_nt != 0, pre ? (char *) c->ws + st.aux_off : nullptr, pre ? c->ws_size - st.aux_off : 0);
+                c->st.kernel_launches += nl + (pre ? 1 : 0);
+                return 1;
+            }
             if (!is_quant(a->type)) {
                 timed_scope ts(c, "mul_mat_f", (double) ggml_abi_nbytes(a));
                 launch_mul_mat_f(s, TD(a), TD(b), TD(n), (float *) ((char *) c->ws + st.aux_off), c->ws ? c->ws_size - st.aux_off : 0);

@@ -182,6 +182,14 @@ void launch_qkv(hipStream_t s, const qkv_args & a, int type_a, int type_b);
 // src1 rounded to f16 first when src0 is f16 (ggml-cpu vec_dot_type semantics)
 void launch_mul_mat_f(hipStream_t s, const tdesc & src0, const tdesc & src1, const tdesc & dst, float * ws = nullptr, size_t ws_bytes = 0);  // ws: scratch for K-split partial tiles
 size_t mul_mat_f_workspace_bytes(const tdesc & src0, const tdesc & src1);
+// ---- bf16 src0 (mmbf.hip): launch_mul_mat_f hands a bf16 matrix on to launch_mul_mat_bf16.  The form is decided in ONE place (mul_mat_bf16_form: the streaming
+// mat-vec for 1 column, its multi-column form up to the hand-over, 16 x 16 tiles, 32 x 32 tiles, the dot kernel for what is not 16-byte aligned)
+enum { MI_BF16_DOT = 0, MI_BF16_MMV = 1, MI_BF16_MMV_COLS = 2, MI_BF16_MMA16 = 3, MI_BF16_MMA = 4 };
+int mul_mat_bf16_form(const tdesc & src0, const tdesc & src1, const tdesc & dst, int force, int max_cols);
+const char * mul_mat_bf16_class(int form, int64_t n_cols);  // timing class of a form
+int mul_mat_bf16_launches(int form, const tdesc & src0, const tdesc & src1);
+void launch_mul_mat_bf16(hipStream_t s, const tdesc & src0, const tdesc & src1, const tdesc & dst, int form = -1, bool nt = MI_BF16_NT != 0, void * ws = nullptr, size_t ws_bytes = 0);
+size_t mul_mat_bf16_workspace_bytes(const tdesc & src0, const tdesc & src1);  // the 32 x 32 tile form with src1 rounded once into scratch (option bf16_preround)
 // ---- non-flash attention chain of a small batch over position lists (attn_nf.hip)
 size_t attn_nf_list_scratch_bytes(const tdesc & q, const tdesc & k, int * dq_out);
 bool launch_attn_nf_list(hipStream_t s, const tdesc & q, const tdesc & k, const tdesc & v, const tdesc & mask, const tdesc & dst, const int * lists, int list_stride,
@@ -399,6 +407,7 @@ void tu_touch_quantize(hipStream_t s);
 void tu_touch_mmvq(hipStream_t s);
 void tu_touch_qkv(hipStream_t s);
 void tu_touch_mmf(hipStream_t s);
+void tu_touch_mmbf(hipStream_t s);
 void tu_touch_attn_nf(hipStream_t s);
 void tu_touch_mmq(hipStream_t s);
 void tu_touch_mmq_i8(hipStream_t s);
@@ -419,6 +428,7 @@ inline void preload_kernel_files(hipStream_t s) {
     tu_touch_mmid(s);
     tu_touch_qkv(s);
     tu_touch_mmf(s);
+    tu_touch_mmbf(s);
     tu_touch_attn_nf(s);
     tu_touch_mmq(s);
     tu_touch_mmq_i8(s);

@@ -693,6 +693,10 @@ template <int G> static void launch_gqa_t(hipStream_t s, const tdesc & a, const 
 }
 
 void launch_mul_mat_f(hipStream_t s, const tdesc & a, const tdesc & b, const tdesc & d, float * ws, size_t ws_bytes) {
+    if (a.type == GGML_TYPE_BF16) {  // a weight matrix kept in bf16: its own kernels and routing (mmbf.hip)
+        launch_mul_mat_bf16(s, a, b, d);
+        return;
+    }
     const int64_t K = a.ne[0];
     const bool w16 = a.type == GGML_TYPE_F16;
     const int esz = w16 ? 2 : 4;

@@ -16,6 +16,7 @@
 #include <hip/hip_runtime.h>
 
 #include "mmvq_types.h"
+#include "kv_quant.h"
 
 namespace mi355x {
 
@@ -88,9 +89,12 @@ __global__ void __launch_bounds__(256) k_mmid(const mmid_args a) {
     }
 }
 
-// f16 / f32 experts: k_mul_mat_f's product (f32 activations rounded to f16 first when the weights are f16, f32 fmaf accumulation), one wave per row
-template <bool W16>
+// f16 / bf16 / f32 experts: k_mul_mat_f's product (f32 activations rounded to the weights' 16-bit format first — f16, or bf16 through f2bf as ggml-cpu's
+// from_float does —, f32 fmaf accumulation), one wave per row.  WT: 0 f32, 1 f16, 2 bf16
+__device__ __forceinline__ float mmid_bf2f(const uint16_t h) { return __uint_as_float((uint32_t) h << 16); }
+template <int WT>
 __global__ void __launch_bounds__(256) k_mmid_f(const mmid_args a, const int vec_ok) {
+    constexpr bool W16 = WT == 1, WBF = WT == 2;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int row = blockIdx.x * 4 + wave;
     const int pair = blockIdx.y, tok = pair / a.n_used, slot = pair - tok * a.n_used;
@@ -108,13 +112,13 @@ __global__ void __launch_bounds__(256) k_mmid_f(const mmid_args a, const int vec
     if (vec_ok) {
         for (int k = lane * 8; k < K; k += 64 * 8) {
             float w[8];
-            if (W16) {
+            if (W16 || WBF) {
                 const uint4 t = *(const uint4 *) (wrow + (size_t) k * 2);
                 const uint32_t u[4] = {t.x, t.y, t.z, t.w};
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
-                    w[2 * i] = h2f((uint16_t) (u[i] & 0xFFFF));
-                    w[2 * i + 1] = h2f((uint16_t) (u[i] >> 16));
+                    w[2 * i] = WBF ? mmid_bf2f((uint16_t) (u[i] & 0xFFFF)) : h2f((uint16_t) (u[i] & 0xFFFF));
+                    w[2 * i + 1] = WBF ? mmid_bf2f((uint16_t) (u[i] >> 16)) : h2f((uint16_t) (u[i] >> 16));
                 }
             } else {
                 const float4 t0 = *(const float4 *) (wrow + (size_t) k * 4), t1 = *(const float4 *) (wrow + (size_t) k * 4 + 16);
@@ -123,13 +127,14 @@ __global__ void __launch_bounds__(256) k_mmid_f(const mmid_args a, const int vec
             const float4 x0 = *(const float4 *) (xcol + (size_t) k * 4), x1 = *(const float4 *) (xcol + (size_t) k * 4 + 16);
             const float x[8] = {x0.x, x0.y, x0.z, x0.w, x1.x, x1.y, x1.z, x1.w};
 #pragma unroll
-            for (int i = 0; i < 8; ++i) acc = fmaf(w[i], W16 ? h2f(f2h(x[i])) : x[i], acc);
+            for (int i = 0; i < 8; ++i) acc = fmaf(w[i], WBF ? mmid_bf2f(f2bf(x[i])) : (W16 ? h2f(f2h(x[i])) : x[i]), acc);
         }
     } else {
         for (int k = lane; k < K; k += 64) {
-            const float wv = W16 ? h2f(*(const uint16_t *) (wrow + (size_t) k * 2)) : *(const float *) (wrow + (size_t) k * 4);
+            const float wv = WBF ? mmid_bf2f(*(const uint16_t *) (wrow + (size_t) k * 2)) : (W16 ? h2f(*(const uint16_t *) (wrow + (size_t) k * 2)) : *(const float *) (wrow + (size_t) k * 4));
             float xv = *(const float *) (xcol + (size_t) k * 4);
             if (W16) xv = h2f(f2h(xv));
+            if (WBF) xv = mmid_bf2f(f2bf(xv));
             acc = fmaf(wv, xv, acc);
         }
     }
@@ -171,12 +176,13 @@ void launch_mmid(hipStream_t s, const mmid_args & a) {
         case GGML_TYPE_Q5_0: launch_mmid_t<T_Q50>(s, a); break;
         case GGML_TYPE_Q5_1: launch_mmid_t<T_Q51>(s, a); break;
         case GGML_TYPE_IQ4_NL: launch_mmid_t<T_IQ4NL>(s, a); break;
-        case GGML_TYPE_F16: case GGML_TYPE_F32: {
+        case GGML_TYPE_F16: case GGML_TYPE_BF16: case GGML_TYPE_F32: {
             const bool w16 = a.type == GGML_TYPE_F16;
             const bool vec_ok = (a.K % 8) == 0 && ((((uintptr_t) a.W) | ((uintptr_t) a.x) | (uintptr_t) a.w_nb1 | (uintptr_t) a.w_nb2 | (uintptr_t) a.x_nb1 | (uintptr_t) a.x_nb2) & 15) == 0;
             const dim3 grid((unsigned) ((a.N + 3) / 4), (unsigned) (a.n_used * a.n_tokens));
-            if (w16) hipLaunchKernelGGL(k_mmid_f<true>, grid, dim3(256), 0, s, a, vec_ok ? 1 : 0);
-            else hipLaunchKernelGGL(k_mmid_f<false>, grid, dim3(256), 0, s, a, vec_ok ? 1 : 0);
+            if (w16) hipLaunchKernelGGL(k_mmid_f<1>, grid, dim3(256), 0, s, a, vec_ok ? 1 : 0);
+            else if (a.type == GGML_TYPE_BF16) hipLaunchKernelGGL(k_mmid_f<2>, grid, dim3(256), 0, s, a, vec_ok ? 1 : 0);
+            else hipLaunchKernelGGL(k_mmid_f<0>, grid, dim3(256), 0, s, a, vec_ok ? 1 : 0);
             break;
         }
         default: MI_ERR("launch_mmid: unsupported expert type %d", a.type); abort();

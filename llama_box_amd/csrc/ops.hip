@@ -340,6 +340,7 @@ __device__ __forceinline__ float dequant_elem(const int type, const uint8_t * __
     switch (type) {
         case GGML_TYPE_F32: return ((const float *) row)[i];
         case GGML_TYPE_F16: return h2f(((const uint16_t *) row)[i]);
+        case GGML_TYPE_BF16: return __uint_as_float((uint32_t) ((const uint16_t *) row)[i] << 16);  // (token_embd of a bf16 model: the 16 bits shifted up)
         case GGML_TYPE_Q8_0: {
             const uint8_t * b = row + (i >> 5) * 34;
             return (float) (int8_t) b[2 + (i & 31)] * h2f(ld16(b));

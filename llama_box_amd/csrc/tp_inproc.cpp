@@ -1023,6 +1023,7 @@ static bool same_options(const options & a, const options & b) {
     return a.graphs == b.graphs && a.fusion == b.fusion && a.prologue == b.prologue && a.qkv == b.qkv && a.mmvq_max_cols == b.mmvq_max_cols && a.mmq_min_cols == b.mmq_min_cols &&
            a.mmq_i8 == b.mmq_i8 && a.mm_merge == b.mm_merge && a.ss_partials == b.ss_partials && a.fa_self_merge == b.fa_self_merge && a.attn_nf == b.attn_nf &&
            a.softmax_mm == b.softmax_mm && a.skinny_rope == b.skinny_rope && a.skinny_mix == b.skinny_mix && a.mmq_skinny == b.mmq_skinny && a.mmq_bn == b.mmq_bn &&
+           a.bf16_form == b.bf16_form && a.bf16_mmv_max_cols == b.bf16_mmv_max_cols && a.bf16_nt == b.bf16_nt && a.bf16_preround == b.bf16_preround &&
            a.fa_splits == b.fa_splits && a.fa_wo == b.fa_wo && a.small_uploads == b.small_uploads && a.small_downloads == b.small_downloads && a.timing == b.timing;
 }
 static bool ensure_stage(ip_engine * E, size_t need) {

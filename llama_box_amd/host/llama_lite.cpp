@@ -42,6 +42,13 @@ static uint16_t f32_to_f16(float f) {  // IEEE binary16, round-to-nearest-even
     return (uint16_t) (sign | (base + q));
 }
 
+static uint16_t f32_to_bf16(float f) {  // ggml_compute_fp32_to_bf16: round-to-nearest-even, subnormals kept, NaN kept quiet
+    uint32_t x;
+    memcpy(&x, &f, 4);
+    if ((x & 0x7FFFFFFFu) > 0x7F800000u) return (uint16_t) ((x >> 16) | 64);
+    return (uint16_t) ((x + (0x7FFFu + ((x >> 16) & 1u))) >> 16);
+}
+
 static inline uint64_t splitmix64(uint64_t & s) {
     uint64_t z = (s += 0x9E3779B97F4A7C15ull);
     z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
@@ -331,6 +338,33 @@ static void synth_rows(const synth_spec & sp, int64_t row0, int64_t row1, uint8_
         }
         return;
     }
+    if (sp.type == GGML_TYPE_BF16) {
+        // the F16 recipe's draw — lo + (hi - lo) u01 at the element's own key —, rounded to nearest even into bf16.  A tied output matrix (llm_hparams::peaked) takes
+        // `tie_eighths` of every 8 groups of 32 elements from token_embd's row (row * 7919 + 13) % tie_rows: the same draw under that tensor's key (both tensors are bf16
+        // and the range already carries this tensor's gain, so the tied values are token_embd's times tie_gain up to the rounding)
+        const int64_t n = sp.blocks_per_row;
+        auto draw = [&](int tensor_id, uint64_t elem) {
+            uint64_t s = sp.seed ^ ((uint64_t) tensor_id * 0xD1B54A32D192ED03ull) ^ (elem * 0x9E3779B97F4A7C15ull);
+            return sp.f32_lo + (sp.f32_hi - sp.f32_lo) * u01(splitmix64(s));
+        };
+        for (int64_t r = row0; r < row1; ++r) {
+            for (int64_t i = 0; i < n; ++i) {
+                const uint64_t col = (uint64_t) (i + sp.blk_off);
+                float v;
+                bool tied = false;
+                if (sp.tie_id >= 0) {
+                    const uint64_t gb = (uint64_t) (r + sp.row_off) * (uint64_t) (sp.blocks_per_row_global / 32) + col / 32;
+                    uint64_t pick = sp.seed ^ ((uint64_t) sp.tensor_id * 0xD1B54A32D192ED03ull) ^ (gb * 0x9E3779B97F4A7C15ull) ^ 0xA5A5A5A55A5A5A5Aull;
+                    tied = (int) (splitmix64(pick) & 7) < sp.tie_eighths;
+                }
+                if (tied) v = draw(sp.tie_id, (uint64_t) (((r + sp.row_off) * 7919 + 13) % sp.tie_rows) * (uint64_t) sp.blocks_per_row_global + col);
+                else v = draw(sp.tensor_id, (uint64_t) (r + sp.row_off) * (uint64_t) sp.blocks_per_row_global + col);
+                const uint16_t h = f32_to_bf16(v);
+                memcpy(dst + ((r - row0) * n + i) * 2, &h, 2);
+            }
+        }
+        return;
+    }
     for (int64_t r = row0; r < row1; ++r) {
         for (int64_t b = 0; b < sp.blocks_per_row; ++b) {
             const uint64_t gb = (uint64_t) ((r + sp.row_off) * sp.blocks_per_row_global + b + sp.blk_off);
@@ -402,6 +436,11 @@ extern "C" int llm_preset(const char * name, struct llm_hparams * hp) {
     else if (n == "llama3-8b-q3_k_m") set("llama", 32, 4096, 32, 8, 128, 14336, 128256, 8192, 500000.0f, 1e-5f, 0, 0, LLM_FTYPE_Q3_K_M);
     else if (n == "llama3-70b-q2_k") set("llama", 80, 8192, 64, 8, 128, 28672, 128256, 8192, 500000.0f, 1e-5f, 0, 0, LLM_FTYPE_Q2_K);
     else if (n == "test-qwen2") set("qwen2", 2, 256, 4, 2, 64, 768, 768, 512, 1000000.0f, 1e-6f, GGML_ROPE_TYPE_NEOX, 1, LLM_FTYPE_MIXED);
+    // models stored in bf16 (*-BF16.gguf: every matrix, token_embd and output in bf16; norms and biases f32)
+    else if (n == "test-llama-bf16") set("llama", 3, 256, 4, 2, 64, 512, 512, 512, 10000.0f, 1e-5f, 0, 0, LLM_FTYPE_BF16);
+    else if (n == "test-qwen2-bf16") set("qwen2", 2, 256, 4, 2, 64, 768, 768, 512, 1000000.0f, 1e-6f, GGML_ROPE_TYPE_NEOX, 1, LLM_FTYPE_BF16);
+    else if (n == "tinyllama-1.1b-bf16") set("llama", 22, 2048, 32, 4, 64, 5632, 32000, 2048, 10000.0f, 1e-5f, 0, 0, LLM_FTYPE_BF16);
+    else if (n == "llama3-8b-bf16") set("llama", 32, 4096, 32, 8, 128, 14336, 128256, 8192, 500000.0f, 1e-5f, 0, 0, LLM_FTYPE_BF16);
     else return -1;
     return 0;
 }
@@ -451,6 +490,7 @@ static ggml_type pick_type(const llm_hparams & hp, const char * what, int il) {
         case LLM_FTYPE_Q8_0: return GGML_TYPE_Q8_0;
         case LLM_FTYPE_Q6_K: return GGML_TYPE_Q6_K;
         case LLM_FTYPE_F16: return GGML_TYPE_F16;
+        case LLM_FTYPE_BF16: return GGML_TYPE_BF16;
         case LLM_FTYPE_Q4_K_M:
             if (w == "output") return GGML_TYPE_Q6_K;
             if (w == "attn_v") return more ? GGML_TYPE_Q6_K : (hp.attn_v_q5k_70b ? GGML_TYPE_Q5_K : GGML_TYPE_Q4_K);
@@ -514,6 +554,10 @@ static std::vector<tensor_plan> make_plan(const llm_hparams & hp, int tp_rank, i
         // (llm_hparams::branch_gain: the "-damped" sets use ~1/sqrt(2 n_layer), the depth scaling trained residual networks are initialised with)
         const float bgain = hp.branch_gain > 0.0f ? hp.branch_gain : 0.25f;
         const float gain = name == "token_embd.weight" ? sqrtf((float) hp.n_embd) : (branch_out ? bgain : 1.0f);  // embeddings ~N(0,1)
+        if (type == GGML_TYPE_BF16 && lo == 0.0f && hi == 0.0f) {  // a bf16 matrix: uniform values of variance gain^2 / K, the scale the block formats' rows have
+            hi = gain * sqrtf(3.0f / (float) Kg);
+            lo = -hi;
+        }
         plan.push_back({name, type, ne0, ne1, Kg, row_off, k_off, id++, rowpar, lo, hi, gain});
     };
     add("token_embd.weight", pick_type(hp, "token_embd", 0), E, hp.n_vocab, E, 0, 0, false);
@@ -538,7 +582,8 @@ static std::vector<tensor_plan> make_plan(const llm_hparams & hp, int tp_rank, i
     add("output.weight", pick_type(hp, "output", 0), E, v_l, E, tp_rank * v_l, 0, false);
     if (hp.peaked > 0) {
         // the tied blocks are token_embd's: byte for byte (up to the gain) when the two tensors share a format, else its values re-encoded as Q6_K
-        LLM_ASSERT(ggml_abi_blck_size(plan.back().type) > 1 && (plan.back().type == plan.front().type || (plan.back().type == GGML_TYPE_Q6_K && ggml_abi_blck_size(plan.front().type) == 256)));
+        LLM_ASSERT((plan.back().type == GGML_TYPE_BF16 && plan.front().type == GGML_TYPE_BF16 && hp.n_embd % 32 == 0) ||
+                   (ggml_abi_blck_size(plan.back().type) > 1 && (plan.back().type == plan.front().type || (plan.back().type == GGML_TYPE_Q6_K && ggml_abi_blck_size(plan.front().type) == 256))));
         plan.back().tie_type = plan.front().type;
         plan.back().tie_wscale = plan.front().wscale;
         plan.back().tie_id = plan.front().tensor_id;

@@ -37,6 +37,7 @@ enum llm_ftype {
     LLM_FTYPE_Q2_K = 13,         /* Q2_K base; attn_v, attn_output, ffn_down Q3_K; output Q6_K */
     LLM_FTYPE_Q3_K_S = 14,       /* everything Q3_K, output Q6_K */
     LLM_FTYPE_MIXED_KQ23 = 15,   /* test recipe: cycles Q3_K/Q2_K/Q4_K/Q6_K over the tensors of one tiny model */
+    LLM_FTYPE_BF16 = 16,         /* every matrix, token_embd and output BF16 (norms and biases F32), as a *-BF16.gguf holds a model */
 };
 
 struct llm_hparams {
@@ -55,7 +56,8 @@ struct llm_hparams {
     float branch_gain;      /* gain of attn_output / ffn_down (the residual branches); 0 = the default 0.25.  "-damped" presets: 0.08 / sqrt(2 n_layer) */
 };
 
-/* presets: "tinyllama-1.1b-q8_0", "tinyllama-1.1b-q8_0-peaked", "llama3-8b-q4_k_m", "llama3-70b-q4_k_m", "qwen2-7b-q5_k_m", "test-llama", "test-qwen2";
+/* presets: "tinyllama-1.1b-q8_0", "tinyllama-1.1b-q8_0-peaked", "llama3-8b-q4_k_m", "llama3-70b-q4_k_m", "qwen2-7b-q5_k_m", "test-llama", "test-qwen2",
+   "test-llama-bf16", "test-qwen2-bf16", "tinyllama-1.1b-bf16", "llama3-8b-bf16";
    any of them + "-damped" = peaked 3 + branch_gain 0.08 / sqrt(2 n_layer) */
 int llm_preset(const char * name, struct llm_hparams * hp);
 
