@@ -460,6 +460,8 @@ typedef struct { ggml_fp16_t d; uint8_t qs[16]; } block_iq4_nl;                 
 typedef struct { uint8_t scales[QK_K / 16]; uint8_t qs[QK_K / 4]; ggml_fp16_t d; ggml_fp16_t dmin; } block_q2_K;      /* 84 B */
 typedef struct { uint8_t hmask[QK_K / 8]; uint8_t qs[QK_K / 4]; uint8_t scales[K_SCALE_SIZE]; ggml_fp16_t d; } block_q3_K; /* 110 B */
 typedef struct { ggml_fp16_t d; ggml_fp16_t dmin; uint8_t scales[K_SCALE_SIZE]; uint8_t qs[QK_K / 2]; } block_q4_K;   /* 144 B */
+/* IQ4_XS: 8 sub-blocks of 32 values; six-bit scale ib = nibble ib of scales_l | bit pair ib of scales_h << 4, used as ls - 32; qs[16 ib + j] = IQ4_NL code of value 32 ib + j (low nibble) and 32 ib + 16 + j (high) */
+typedef struct { ggml_fp16_t d; uint16_t scales_h; uint8_t scales_l[QK_K / 64]; uint8_t qs[QK_K / 2]; } block_iq4_xs; /* 136 B */
 typedef struct { ggml_fp16_t d; ggml_fp16_t dmin; uint8_t scales[K_SCALE_SIZE]; uint8_t qh[QK_K / 8]; uint8_t qs[QK_K / 2]; } block_q5_K; /* 176 B */
 typedef struct { uint8_t ql[QK_K / 2]; uint8_t qh[QK_K / 4]; int8_t scales[QK_K / 16]; ggml_fp16_t d; } block_q6_K;   /* 210 B */
 typedef struct { float d; int8_t qs[QK_K]; int16_t bsums[QK_K / 16]; } block_q8_K;                        /* 292 B */
@@ -471,6 +473,7 @@ static_assert(sizeof(block_q4_0) == 18 && sizeof(block_q4_1) == 20 && sizeof(blo
 static_assert(sizeof(block_q2_K) == 84, "q2_K");
 static_assert(sizeof(block_q3_K) == 110, "q3_K");
 static_assert(sizeof(block_q4_K) == 144, "q4_K");
+static_assert(sizeof(block_iq4_xs) == 136, "iq4_xs");
 static_assert(sizeof(block_q5_K) == 176, "q5_K");
 static_assert(sizeof(block_q6_K) == 210, "q6_K");
 static_assert(sizeof(block_q8_K) == 292, "q8_K");
@@ -485,7 +488,7 @@ static_assert(sizeof(struct ggml_tensor) % GGML_MEM_ALIGN == 0, "ggml_tensor ali
 static inline int64_t ggml_abi_blck_size(enum ggml_type t) {
     switch (t) {
         case GGML_TYPE_Q8_0: case GGML_TYPE_Q4_0: case GGML_TYPE_Q4_1: case GGML_TYPE_Q5_0: case GGML_TYPE_Q5_1: case GGML_TYPE_Q8_1: case GGML_TYPE_IQ4_NL: return 32;
-        case GGML_TYPE_Q2_K: case GGML_TYPE_Q3_K: case GGML_TYPE_Q4_K: case GGML_TYPE_Q5_K: case GGML_TYPE_Q6_K: case GGML_TYPE_Q8_K: return 256;
+        case GGML_TYPE_Q2_K: case GGML_TYPE_Q3_K: case GGML_TYPE_Q4_K: case GGML_TYPE_Q5_K: case GGML_TYPE_Q6_K: case GGML_TYPE_Q8_K: case GGML_TYPE_IQ4_XS: return 256;
         default: return 1;
     }
 }
@@ -504,6 +507,7 @@ static inline size_t ggml_abi_type_size(enum ggml_type t) {
         case GGML_TYPE_Q2_K: return 84;
         case GGML_TYPE_Q3_K: return 110;
         case GGML_TYPE_Q4_K: return 144;
+        case GGML_TYPE_IQ4_XS: return 136;
         case GGML_TYPE_Q5_K: return 176;
         case GGML_TYPE_Q6_K: return 210;
         case GGML_TYPE_Q8_K: return 292;

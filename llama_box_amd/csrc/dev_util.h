@@ -89,6 +89,17 @@ typedef uint32_t __attribute__((aligned(2))) u32_a2;
 typedef uint16_t __attribute__((aligned(2))) u16_a2;
 __device__ __forceinline__ uint32_t ld32_a2(const void * p) { return *(const u32_a2 *) p; }
 __device__ __forceinline__ uint16_t ld16(const void * p) { return *(const u16_a2 *) p; }
+// ... and with the 8-byte alignment of IQ4_XS blocks (136 = 8 * 17 bytes): the 8-byte header as one load, 16 bytes of codes as one load at 8 mod 16
+struct __attribute__((packed, aligned(8))) u128_a8 { uint32_t x, y, z, w; };
+__device__ __forceinline__ u128_a8 ld128_a8(const void * p) { return *(const u128_a8 *) p; }
+__device__ __forceinline__ uint2 ld64_a8(const void * p) { return *(const uint2 *) p; }
+// IQ4_XS's table (IQ4_NL's; T_L32 and mmq_q80.hip keep their own copies of the lookup) {-127, -104, -83, -65 | -49, -35, -22, -10 || 1, 13, 25, 38 | 53, 69, 89, 113} applied to the four codes (0 .. 15, one a byte) of a
+// dword: bit 3 of a code picks the 8-entry half, each half is one byte permute over two table dwords
+__device__ __forceinline__ uint32_t iq4nl_bytes(const uint32_t n) {
+    constexpr uint32_t A0 = 0xBFAD9881u, A1 = 0xF6EADDCFu, B0 = 0x26190D01u, B1 = 0x71594535u;
+    const uint32_t s = n & 0x07070707u, m = ((n >> 3) & 0x01010101u) * 0xFFu;
+    return (__builtin_amdgcn_perm(A1, A0, s) & ~m) | (__builtin_amdgcn_perm(B1, B0, s) & m);
+}
 
 __device__ __forceinline__ float silu_f(float x) { return x / (1.0f + expf(-x)); }
 

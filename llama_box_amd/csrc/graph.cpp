@@ -17,13 +17,18 @@
 namespace mi355x {
 
 static bool is_kq23_type(int t) { return t == GGML_TYPE_Q2_K || t == GGML_TYPE_Q3_K; }
-static bool is_quant(int t) { return t == GGML_TYPE_Q4_K || t == GGML_TYPE_Q5_K || t == GGML_TYPE_Q6_K || t == GGML_TYPE_Q8_0 || is_l32_type(t) || is_kq23_type(t); }
+static bool is_iq4xs_type(int t) { return t == GGML_TYPE_IQ4_XS; }
+static bool is_quant(int t) { return t == GGML_TYPE_Q4_K || t == GGML_TYPE_Q5_K || t == GGML_TYPE_Q6_K || t == GGML_TYPE_Q8_0 || is_l32_type(t) || is_kq23_type(t) || is_iq4xs_type(t); }
+// the formats whose acceptance goes through l32_layout_ok
+static bool needs_layout_check(int t) { return is_l32_type(t) || is_kq23_type(t) || is_iq4xs_type(t); }
 // what the kernels over those formats assume of a matrix beyond contiguous rows: every block starts at the format's own alignment (2 bytes; 4 for the offset
 // formats, whose blocks are 20 / 24 bytes) — base address (null while the loader probes a type with a plain tensor: any real allocation is aligned), row and
 // matrix strides.  Their weights live in ordinary device buffers only: the split (-sm row) and row-parallel buffer types keep refusing them.
 // (Q2_K / Q3_K come under the same conditions: 84-byte blocks are read as dwords, 110-byte blocks at 2 bytes; a view may start one block into its parent)
+// (IQ4_XS too, at 8 bytes: its 136 = 8 * 17 byte blocks are read as one aligned 8-byte header and 16-byte pieces at 8 mod 16 — what every whole-block view of an
+// aligned allocation has)
 static bool l32_layout_ok(const ggml_tensor * a) {
-    const size_t al = (a->type == GGML_TYPE_Q4_1 || a->type == GGML_TYPE_Q5_1 || a->type == GGML_TYPE_Q2_K) ? 4 : 2;
+    const size_t al = is_iq4xs_type(a->type) ? 8 : ((a->type == GGML_TYPE_Q4_1 || a->type == GGML_TYPE_Q5_1 || a->type == GGML_TYPE_Q2_K) ? 4 : 2);
     if ((((uintptr_t) a->data) % al) || (a->nb[1] % al) || (a->nb[2] % al) || (a->nb[3] % al)) return false;
     return !buffer_is_rowpar(a->view_src ? a->view_src->buffer : a->buffer) && !buffer_is_split(a->buffer);
 }
@@ -35,7 +40,8 @@ static bool l32_layout_ok(const ggml_tensor * a) {
 static inline int mmq_min_cols_for(const backend_ctx * c, int wtype) {
     // Q2_K / Q3_K: the mat-vec kernel serves 2 .. 8 columns in one pass; from 9 the tiled matrix-core kernel (no skinny or wide form reads these layouts).
     // The hand-over was set where the one-pass form ends and not compared with other thresholds.
-    if (is_kq23_type(wtype)) return 9;
+    // IQ4_XS: the same hand-over, taken from Q2_K / Q3_K and not compared with other thresholds either.
+    if (is_kq23_type(wtype) || is_iq4xs_type(wtype)) return 9;
     if (c->opt.mmq_min_cols != 3) return c->opt.mmq_min_cols;
     return (wtype == GGML_TYPE_Q4_K || (wtype == GGML_TYPE_Q6_K && !c->mm_q5_major)) ? 2 : 3;
 }
@@ -126,7 +132,7 @@ static bool mm_id_ok(const ggml_tensor * op) {
     const ggml_tensor * ids = op->src[2];
     if (!a || !b || !ids || b->type != GGML_TYPE_F32 || ids->type != GGML_TYPE_I32 || op->type != GGML_TYPE_F32 || !ggml_abi_is_contiguous(op)) return false;
     if (!(is_quant(a->type) || a->type == GGML_TYPE_F16 || a->type == GGML_TYPE_BF16 || a->type == GGML_TYPE_F32) || !rows_contig(a) || a->ne[3] != 1 || a->ne[0] % ggml_abi_blck_size(a->type) != 0) return false;
-    if ((is_l32_type(a->type) || is_kq23_type(a->type)) && !l32_layout_ok(a)) return false;
+    if (needs_layout_check(a->type) && !l32_layout_ok(a)) return false;
     if (buffer_is_rowpar(a->view_src ? a->view_src->buffer : a->buffer)) return false;  // (row-parallel weights hold a slice of every row: MUL_MAT only)
     if (b->ne[0] != a->ne[0] || b->nb[0] != 4 || b->ne[3] != 1 || (b->nb[1] % 4) || (b->nb[2] % 4)) return false;
     if (ids->nb[0] != 4 || (ids->nb[1] % 4) || ids->ne[2] != 1 || ids->ne[3] != 1 || ids->ne[1] != b->ne[2] || ids->ne[0] < 1 || ids->ne[1] < 1) return false;
@@ -155,7 +161,7 @@ bool supports_op(const ggml_tensor * op) {
             if (buffer_is_split(a->buffer)) return split_mul_mat_supported(op);  // -sm row weights: every device computes its rows (split.cpp)
             if (mm_cache_image_ok(op)) return true;
             if (is_quant(a->type)) {
-                if ((is_l32_type(a->type) || is_kq23_type(a->type)) && !l32_layout_ok(a)) return false;
+                if (needs_layout_check(a->type) && !l32_layout_ok(a)) return false;
                 return a->ne[2] == 1 && a->ne[3] == 1 && rows_contig(a) && b->nb[0] == 4 && a->ne[0] % ggml_abi_blck_size(a->type) == 0;
             }
             if (a->type == GGML_TYPE_F16 || a->type == GGML_TYPE_F32) return true;
@@ -196,7 +202,7 @@ bool supports_op(const ggml_tensor * op) {
             return (st == GGML_TYPE_F32 || st == GGML_TYPE_F16) && (dt == GGML_TYPE_F32 || dt == GGML_TYPE_F16);
         }
         case GGML_OP_GET_ROWS:
-            if ((is_l32_type(a->type) || is_kq23_type(a->type)) && !l32_layout_ok(a)) return false;  // (token_embd in q4_0 / q2_K / q3_K ...: the block alignment and buffer types of the MUL_MAT arm)
+            if (needs_layout_check(a->type) && !l32_layout_ok(a)) return false;  // (token_embd in q4_0 / q2_K / q3_K / iq4_xs ...: the block alignment and buffer types of the MUL_MAT arm)
             return b->type == GGML_TYPE_I32 && op->type == GGML_TYPE_F32 && rows_contig(a) && op->nb[0] == 4 &&
                    (is_quant(a->type) || a->type == GGML_TYPE_F16 || a->type == GGML_TYPE_BF16 || a->type == GGML_TYPE_F32);
         case GGML_OP_SET_ROWS:
@@ -500,6 +506,7 @@ static const char * type_tag(int t) {
         case GGML_TYPE_Q5_0: return "q5_0";
         case GGML_TYPE_Q5_1: return "q5_1";
         case GGML_TYPE_IQ4_NL: return "iq4_nl";
+        case GGML_TYPE_IQ4_XS: return "iq4_xs";
         case GGML_TYPE_BF16: return "bf16";
         default: return "f";
     }
@@ -516,7 +523,7 @@ static bool run_mul_mat_q(exec_state & st, const ggml_tensor * w, const ggml_ten
     const int64_t K = w->ne[0], N = w->ne[1];
     const int64_t M = b->ne[1] * b->ne[2] * b->ne[3];
     const double wbytes = (double) ggml_abi_row_size(w->type, K) * (double) N * (w2 ? 2.0 : 1.0);
-    const bool kquant = is_kq23_type(w->type) || w->type == GGML_TYPE_Q4_K || w->type == GGML_TYPE_Q5_K || w->type == GGML_TYPE_Q6_K || (w->type == GGML_TYPE_Q8_0 && (K % 256) == 0);  // formats with the mat-vec prologue
+    const bool kquant = is_kq23_type(w->type) || is_iq4xs_type(w->type) || w->type == GGML_TYPE_Q4_K || w->type == GGML_TYPE_Q5_K || w->type == GGML_TYPE_Q6_K || (w->type == GGML_TYPE_Q8_0 && (K % 256) == 0);  // formats with the mat-vec prologue
     auto dn = st.deferred.find(b);
     const bool pro_norm = dn != st.deferred.end();
     const bool pro_fa = st.fa_wo.b == b && st.fa_wo.part != nullptr;  // (set by the FLASH_ATTN_EXT node after checking this very mat-vec)
@@ -798,7 +805,7 @@ static bool can_defer_norm(const exec_state & st, int i, const ggml_tensor * n, 
         for (int s = 0; s < GGML_MAX_SRC; ++s) {
             if (t->src[s] != m) continue;
             const ggml_tensor * wt = t->src[0];
-            const bool ok = t->op == GGML_OP_MUL_MAT && s == 1 && (is_kq23_type(wt->type) || wt->type == GGML_TYPE_Q4_K || wt->type == GGML_TYPE_Q5_K || wt->type == GGML_TYPE_Q6_K || wt->type == GGML_TYPE_Q8_0) &&
+            const bool ok = t->op == GGML_OP_MUL_MAT && s == 1 && (is_kq23_type(wt->type) || is_iq4xs_type(wt->type) || wt->type == GGML_TYPE_Q4_K || wt->type == GGML_TYPE_Q5_K || wt->type == GGML_TYPE_Q6_K || wt->type == GGML_TYPE_Q8_0) &&
                             wt->ne[2] == 1 && wt->ne[3] == 1 && ggml_abi_is_contiguous(t) && !(st.c->tp && buffer_is_rowpar(wt->view_src ? wt->view_src->buffer : wt->buffer)) &&
                             !buffer_is_split(wt->buffer);  // (a split weight's devices are sent the f32 row: it has to be written)
             if (!ok) return false;

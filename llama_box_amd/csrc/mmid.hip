@@ -176,6 +176,7 @@ void launch_mmid(hipStream_t s, const mmid_args & a) {
         case GGML_TYPE_Q5_0: launch_mmid_t<T_Q50>(s, a); break;
         case GGML_TYPE_Q5_1: launch_mmid_t<T_Q51>(s, a); break;
         case GGML_TYPE_IQ4_NL: launch_mmid_t<T_IQ4NL>(s, a); break;
+        case GGML_TYPE_IQ4_XS: launch_mmid_t<T_IQ4XS>(s, a); break;
         case GGML_TYPE_F16: case GGML_TYPE_BF16: case GGML_TYPE_F32: {
             const bool w16 = a.type == GGML_TYPE_F16;
             const bool vec_ok = (a.K % 8) == 0 && ((((uintptr_t) a.W) | ((uintptr_t) a.x) | (uintptr_t) a.w_nb1 | (uintptr_t) a.w_nb2 | (uintptr_t) a.x_nb1 | (uintptr_t) a.x_nb2) & 15) == 0;

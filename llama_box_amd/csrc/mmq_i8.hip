@@ -1,5 +1,6 @@
 // mmq_i8.hip — batched mat-mul (3 columns and up: continuous-batching decode steps, prompt micro-batches) for Q4_K, Q5_K and
-// Q6_K weights — and, from 9 columns, Q2_K (one piece, sc * level) and Q3_K (two: the level is split) — on the gfx950 INTEGER matrix cores.
+// Q6_K weights — and, from 9 columns, Q2_K (one piece, sc * level), Q3_K (two: the level is split) and IQ4_XS (two: the product is split, as Q6_K's) — on
+// the gfx950 INTEGER matrix cores.
 //
 // Same contract as mmq.hip (ggml-cpu's ggml_vec_dot_q{4,5}_K_q8_K: integer block sums on Q8_K activations, one f32
 // scale-accumulate per super-block — SURVEY.md §8a row a6), but the block sums are computed by v_mfma_i32_32x32x32_i8:
@@ -18,7 +19,8 @@
 // the MFMAs of trip t run, one barrier per trip.  BN = 128 (8 waves) or 64 (4 waves; used when the grid would not
 // fill 256 CUs otherwise); each wave owns 32 weight rows x 64 activation columns (BM = 128), or all 64 / 32 columns of a
 // small batch with the K steps of a trip shared between two wave groups (BM = 64 / 32).  Q6_K splits the PRODUCT
-// (q - 32) * sc = 64 * p1 + p0 instead of the scale.  Up to three matrices over the same activations share a launch.
+// (q - 32) * sc = 64 * p1 + p0 instead of the scale, and so does IQ4_XS (QT = 23, its ggml type id): (ls - 32) * table value in -3937 .. 4064 = 64 * p1 + p0
+// with p0 in 0 .. 63 and p1 in -62 .. 63.  Up to three matrices over the same activations share a launch.
 #include <algorithm>
 
 #include "dev_util.h"
@@ -60,11 +62,12 @@ template <int QT, int BN, int BM = 128>
 __global__ void __launch_bounds__(BN * 4, BN == 64 ? (BM == 32 ? 3 : 2) : 1) k_mmq_i8(const mmq8_args a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int NT = BN * 4;
+    static_assert(QT == 2 || QT == 3 || QT == 4 || QT == 5 || QT == 6 || QT == 23, "weight format");
     constexpr int NP = QT == 5 ? 3 : (QT == 2 ? 1 : 2);
-    constexpr int BYTES = QT == 2 ? 84 : (QT == 3 ? 110 : (QT == 4 ? 144 : (QT == 5 ? 176 : 210)));
-    constexpr bool Q6 = QT == 6, Q2 = QT == 2, Q3 = QT == 3;
+    constexpr int BYTES = QT == 2 ? 84 : (QT == 3 ? 110 : (QT == 4 ? 144 : (QT == 5 ? 176 : (QT == 23 ? 136 : 210))));
+    constexpr bool Q6 = QT == 6, Q2 = QT == 2, Q3 = QT == 3, XS = QT == 23;
     constexpr bool NIB = QT == 4 || QT == 5;  // nibble formats: 32-value sub-blocks, digits of the scale
-    constexpr bool NOMIN = Q6 || Q3;          // no mins term: the 16-wide f16 step is skipped
+    constexpr bool NOMIN = Q6 || Q3 || XS;    // no mins term: the 16-wide f16 step is skipped
     constexpr int TA = BN * 128, TB = BM * 128, STAGE = NP * TA + TB;
     constexpr int NBC = (BM * 8) / NT;  // 16-byte activation chunks per thread per trip (1, 2 or 4)
     constexpr int NTT = BM >= 64 ? 2 : 1;  // 32-column tiles per wave
@@ -147,6 +150,13 @@ __global__ void __launch_bounds__(BN * 4, BN == 64 ? (BM == 32 ? 3 : 2) : 1) k_m
             g6_sc1 = ld32_a2(blk + 100);
             g6_ql2 = ld32_a2(blk + 104);
             g6_d = ld16(blk + 108);
+        } else if constexpr (XS) {
+            // half h of an IQ4_XS block: this thread owns sub-block 4h + aq, the 16 bytes qs[16 (4h + aq) ..]; 8-byte aligned blocks
+            const uint2 hd = ld64_a8(blk);
+            g6_sc0 = hd.x;  // d | scales_h << 16
+            g6_sc1 = hd.y;  // scales_l[4]
+            const u128_a8 q = ld128_a8(blk + 8 + 64 * h + 16 * aq);
+            g_q = make_uint4(q.x, q.y, q.z, q.w);
         } else {
             // half h of a Q6_K block: ql[64h .. 64h+63], qh[32h .. 32h+31], scales[8h .. 8h+7]; this thread owns l = 8*aq .. 8*aq+7
             g6_ql0 = ld32_a2(blk + 64 * h + 8 * aq);
@@ -215,6 +225,36 @@ __global__ void __launch_bounds__(BN * 4, BN == 64 ? (BM == 32 ? 3 : 2) : 1) k_m
                 *(uint2 *) (buf + off) = make_uint2(o0[0], o0[1]);
                 *(uint2 *) (buf + TA + off) = make_uint2(o1[0], o1[1]);
             }
+        } else if constexpr (XS) {
+            // IQ4_XS: s * v with s = ls - 32 in -32 .. 31 and v from the table in -127 .. 113 spans -3937 .. 4064, so the PRODUCT is split as Q6_K's below:
+            // p = 64 * p1 + p0 with p0 = p & 63 in 0 .. 63 and p1 = p >> 6 in -62 .. 63 — two int8 pieces, exactly the CPU's integers.  The table is looked up
+            // with 127 added (bytes 0 .. 240, unsigned: they widen to 16 bits by a zero fill), and -127 * s rides in the 16-bit constant: s * (v + 127) stays
+            // inside -7680 .. 7440.  This thread: sub-block ib = 4h + aq; low nibbles = its values 0 .. 15 (chunk 2 aq), high = 16 .. 31 (chunk 2 aq + 1).
+            typedef short short2v __attribute__((ext_vector_type(2)));
+            constexpr uint32_t A0 = 0x3E2C1700u, A1 = 0x75695C4Eu, B0 = 0xA5988C80u, B1 = 0xF0D8C4B4u;  // {0, 23, 44, 62 | 78, 92, 105, 117 || 128, 140, 152, 165 | 180, 196, 216, 240}
+            const int ib = 4 * h + aq;
+            const int sc = (int) (((g6_sc1 >> (4 * ib)) & 0xFu) | (((g6_sc0 >> (16 + 2 * ib)) & 3u) << 4)) - 32;
+            const uint32_t scp = ((uint32_t) sc & 0xFFFFu) * 0x00010001u;
+            const uint32_t cp = ((uint32_t) (-127 * sc) & 0xFFFFu) * 0x00010001u;
+            const uint32_t qv[4] = {g_q.x, g_q.y, g_q.z, g_q.w};
+            uint32_t o1[8], o0[8];  // [0 .. 3]: low nibbles, [4 .. 7]: high
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                const uint32_t n = (i < 4 ? qv[i] : (qv[i - 4] >> 4)) & 0x0F0F0F0Fu;
+                const uint32_t s = n & 0x07070707u, m = ((n >> 3) & 0x01010101u) * 0xFFu;
+                const uint32_t u = (__builtin_amdgcn_perm(A1, A0, s) & ~m) | (__builtin_amdgcn_perm(B1, B0, s) & m);  // four table bytes + 127
+                const short2v pa = __builtin_bit_cast(short2v, __builtin_amdgcn_perm(0u, u, 0x0c010c00u)) * __builtin_bit_cast(short2v, scp) + __builtin_bit_cast(short2v, cp);
+                const short2v pb = __builtin_bit_cast(short2v, __builtin_amdgcn_perm(0u, u, 0x0c030c02u)) * __builtin_bit_cast(short2v, scp) + __builtin_bit_cast(short2v, cp);
+                const uint32_t pa1 = __builtin_bit_cast(uint32_t, pa >> (short2v){6, 6}), pb1 = __builtin_bit_cast(uint32_t, pb >> (short2v){6, 6});
+                const uint32_t pa0 = __builtin_bit_cast(uint32_t, pa) & 0x003F003Fu, pb0 = __builtin_bit_cast(uint32_t, pb) & 0x003F003Fu;
+                o1[i] = __builtin_amdgcn_perm(pb1, pa1, 0x06040200u);
+                o0[i] = __builtin_amdgcn_perm(pb0, pa0, 0x06040200u);
+            }
+            const int off_lo = sw_off(arow, 2 * aq), off_hi = sw_off(arow, 2 * aq + 1);
+            *(uint4 *) (buf + off_lo) = make_uint4(o1[0], o1[1], o1[2], o1[3]);
+            *(uint4 *) (buf + off_hi) = make_uint4(o1[4], o1[5], o1[6], o1[7]);
+            *(uint4 *) (buf + TA + off_lo) = make_uint4(o0[0], o0[1], o0[2], o0[3]);
+            *(uint4 *) (buf + TA + off_hi) = make_uint4(o0[4], o0[5], o0[6], o0[7]);
         } else if constexpr (NIB) {
         // ---- weight pieces: this thread owns 16 values of sub-block 2*j2 (low nibbles) and of 2*j2+1 (high nibbles)
         const int j2 = 2 * h + (aq >> 1);
@@ -294,7 +334,7 @@ __global__ void __launch_bounds__(BN * 4, BN == 64 ? (BM == 32 ? 3 : 2) : 1) k_m
         // ---- per-super-block metadata (staged with the second half; consumed at the end of that trip)
         if (h == 1) {
             if constexpr (NOMIN) {
-                if (aq == 0) dd[arow] = make_float2(h2f(g6_d), 0.0f);
+                if (aq == 0) dd[arow] = make_float2(h2f(XS ? (uint16_t) (g6_sc0 & 0xFFFFu) : g6_d), 0.0f);
                 if (tid < BM) dyv[tid] = g_dy;
             }
             if (Q2 && aq == 0) {
@@ -393,7 +433,7 @@ __global__ void __launch_bounds__(BN * 4, BN == 64 ? (BM == 32 ? 3 : 2) : 1) k_m
                 else if constexpr (QT == 5) {
                     is0 = (acc[0][t][r] << 4) + (acc[1][t][r] << 2) + acc[2][t][r];
                     is1 = (acc[0][t][r + 1] << 4) + (acc[1][t][r + 1] << 2) + acc[2][t][r + 1];
-                } else { is0 = (acc[0][t][r] << 6) + acc[1][t][r]; is1 = (acc[0][t][r + 1] << 6) + acc[1][t][r + 1]; }
+                } else { static_assert(Q6 || XS, "fold"); is0 = (acc[0][t][r] << 6) + acc[1][t][r]; is1 = (acc[0][t][r + 1] << 6) + acc[1][t][r + 1]; }  // Q6_K, IQ4_XS: 64 * p1 + p0
 #if MMQ_FOLD_PACKED
                 float2v v = (float2v){(float) is0, (float) is1} * (float2v){sd.x, sd.z};
                 if constexpr (!NOMIN) v = __builtin_elementwise_fma(-(float2v){sd.y, sd.w}, (float2v){am[r], am[r + 1]}, v);
@@ -476,8 +516,8 @@ __global__ void __launch_bounds__(BN * 4, BN == 64 ? (BM == 32 ? 3 : 2) : 1) k_m
 
 bool mmq_i8_supported(int type, int64_t K, int64_t N, int64_t M) {
     (void) N;
-    // (Q2_K / Q3_K: the tiled form only, from the 9 columns the mat-vec passes end at — graph.cpp: mmq_min_cols_for)
-    if (type == GGML_TYPE_Q2_K || type == GGML_TYPE_Q3_K) return (K % 256) == 0 && M >= 9;
+    // (Q2_K / Q3_K / IQ4_XS: the tiled form only, from the 9 columns the mat-vec passes end at — graph.cpp: mmq_min_cols_for)
+    if (type == GGML_TYPE_Q2_K || type == GGML_TYPE_Q3_K || type == GGML_TYPE_IQ4_XS) return (K % 256) == 0 && M >= 9;
     return (type == GGML_TYPE_Q4_K || type == GGML_TYPE_Q5_K || type == GGML_TYPE_Q6_K) && (K % 256) == 0 && M >= 2;
 }
 
@@ -499,6 +539,8 @@ template <int QT, int BN, int BM = 128> static void launch_mmq8_t(hipStream_t s,
 // few activation columns (continuous-batching decode, M <= 64) leave N/64 x 1 workgroups — far fewer than 256 CUs — so
 // the K range is split over blockIdx.y and the partial products are summed in a fixed order by a second tiny kernel
 int mmq_pick_ksplit(int64_t K, int64_t N, int64_t M, bool skinny, int type) {
+    // (Q2_K / Q3_K / IQ4_XS reach this line too although the tile kernel, not the skinny one, serves their 9 .. 32 columns: the BM 32 form inherits the skinny
+    // kernel's K split — always a power of two, summed by the same reduction — and mmq_wide_tiles below answers 0 for them.  Inherited, not measured for them.)
     if (skinny && M >= 2 && M <= 32 && (N % 32) == 0) return mmq_skinny_ksplit(K, N);
     // prompt batches the wide form of mmq_skinny.hip serves run without a K split (its grid fills the chip by token-tile groups)
     if (skinny && mmq_wide_tiles(type, K, &N, 1, M, (K / 256) * (type == GGML_TYPE_Q4_K ? 144 : 176), 1) != 0) return 1;
@@ -657,7 +699,7 @@ int launch_mmq_i8_multi(hipStream_t s, int type, int n_mat, const mmq_mat_desc *
         else launch_mmq8_t<QT, 64, 64>(s, a);            \
     }
         if (type == GGML_TYPE_Q4_K) MMQ_SKINNY(4) else if (type == GGML_TYPE_Q5_K) MMQ_SKINNY(5) else if (type == GGML_TYPE_Q6_K) MMQ_SKINNY(6)
-        else if (type == GGML_TYPE_Q2_K) MMQ_SKINNY(2) else if (type == GGML_TYPE_Q3_K) MMQ_SKINNY(3)
+        else if (type == GGML_TYPE_Q2_K) MMQ_SKINNY(2) else if (type == GGML_TYPE_Q3_K) MMQ_SKINNY(3) else if (type == GGML_TYPE_IQ4_XS) MMQ_SKINNY(23)
         else { MI_ERR("launch_mmq_i8_multi: unsupported weight type %d", type); abort(); }
 #undef MMQ_SKINNY
     } else if (type == GGML_TYPE_Q4_K) {
@@ -675,6 +717,9 @@ int launch_mmq_i8_multi(hipStream_t s, int type, int n_mat, const mmq_mat_desc *
     } else if (type == GGML_TYPE_Q3_K) {
         if (bn == 128) launch_mmq8_t<3, 128>(s, a);
         else launch_mmq8_t<3, 64>(s, a);
+    } else if (type == GGML_TYPE_IQ4_XS) {
+        if (bn == 128) launch_mmq8_t<23, 128>(s, a);
+        else launch_mmq8_t<23, 64>(s, a);
     } else {
         MI_ERR("launch_mmq_i8_multi: unsupported weight type %d", type);
         abort();

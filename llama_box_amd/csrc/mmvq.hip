@@ -526,8 +526,8 @@ template <typename T> static void launch_type(hipStream_t s, const mmvq_args & a
         }
         if (a0.fa_part) {
             if (glu || a0.norm_w || a0.fa_splits < 1 || a0.fa_splits > 16) { MI_ERR("launch_mmvq: bad attention-partials prologue request"); abort(); }
-            // (Q2_K / Q3_K: graph.cpp leaves the combine pass its own launch — the form is not built for them, no test model reaches it)
-            if constexpr (std::is_same<T, T_Q2K>::value || std::is_same<T, T_Q3K>::value) { MI_ERR("launch_mmvq: weight type %d has no attention-partials prologue", a0.type); abort(); }
+            // (Q2_K / Q3_K / IQ4_XS: graph.cpp leaves the combine pass its own launch — the form is not built for them, no test model reaches it)
+            if constexpr (std::is_same<T, T_Q2K>::value || std::is_same<T, T_Q3K>::value || std::is_same<T, T_IQ4XS>::value) { MI_ERR("launch_mmvq: weight type %d has no attention-partials prologue", a0.type); abort(); }
             else launch_stream<T, false, 3>(s, a0);
             return;
         }
@@ -616,6 +616,7 @@ void launch_mmvq(hipStream_t s, const mmvq_args & a, int rows_per_wave) {
         case GGML_TYPE_Q5_0: launch_type<T_Q50>(s, a, rows_per_wave); break;
         case GGML_TYPE_Q5_1: launch_type<T_Q51>(s, a, rows_per_wave); break;
         case GGML_TYPE_IQ4_NL: launch_type<T_IQ4NL>(s, a, rows_per_wave); break;
+        case GGML_TYPE_IQ4_XS: launch_type<T_IQ4XS>(s, a, rows_per_wave); break;
         default: MI_ERR("launch_mmvq: unsupported weight type %d", a.type); abort();
     }
 }

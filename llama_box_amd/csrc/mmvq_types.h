@@ -323,6 +323,62 @@ struct T_Q3K {
     }
 };
 
+// ------------------------------------------------------------------------------------------------ IQ4_XS
+// {d, scales_h, scales_l[4], qs[128]} = 136 bytes: IQ4_NL's 16-entry table under a K-quant frame of 8 sub-blocks of 32 values, six-bit scales used as ls - 32,
+// no mins (bsums are not read).  Q4_K's lane mapping: 4 lanes per super-block, lane j owns sub-blocks 2j and 2j + 1 = qs[32 j .. 32 j + 31] as two 16-byte
+// loads, plus the 8-byte header as one load shared by the block's four lanes through the cache; K = 4096 is one trip of a wave.  Blocks are 8-byte aligned
+// (graph.cpp: l32_layout_ok), so the header is an aligned 8-byte load and the codes are 16-byte loads at 8 mod 16, which gfx950 serves as dwordx4.
+// NOT Q4_K's nibble order: bytes 16 ib .. 16 ib + 15 carry values 0 .. 15 of sub-block ib in their low nibbles and values 16 .. 31 in their high ones, so a
+// lane's four 16-byte activation pieces meet (q0 low, q0 high, q1 low, q1 high) in that order.  Codes become table bytes through two byte permutes a dword and
+// meet the int8 activations in v_dot4_i32_i8; the sub-block sum (|sum| <= 32 * 127 * 127 < 2^19) is multiplied by ls - 32 in int32; one f32 term per lane
+// follows, (d * dy) * isum, where the reference adds (d * dy * (ls - 32)) * sumi per sub-block.
+struct T_IQ4XS {
+    typedef q8k_dev act;
+    static constexpr int BLK = 256, BYTES = 136, PPB = 4;
+    struct raw { u128_a8 q0, q1; uint2 hdr; };  // hdr.x = d | scales_h << 16, hdr.y = scales_l[4]
+    static constexpr int DW = 10;
+    static __device__ __forceinline__ raw load(const uint8_t * __restrict__ row, int p, int = 0) {
+        const uint8_t * blk = row + (size_t) (p >> 2) * BYTES;
+        raw r;
+        r.hdr = ld64_a8(blk);
+        r.q0 = ld128_a8(blk + 8 + 32 * (p & 3));
+        r.q1 = ld128_a8(blk + 24 + 32 * (p & 3));
+        return r;
+    }
+    template <int NC> static __device__ __forceinline__ void dot(const raw & r, int p, const act * __restrict__ y, int nblk, float * acc) {
+        const int b = p >> 2, j = p & 3;
+        const float d = h2f((uint16_t) (r.hdr.x & 0xFFFFu));
+        // scales 2j and 2j + 1: the two nibbles of scales_l[j], bit pairs 2j and 2j + 1 of scales_h
+        const uint32_t sl = (r.hdr.y >> (8 * j)) & 0xFFu, sh = (r.hdr.x >> (16 + 4 * j)) & 0xFu;
+        const int s0 = (int) ((sl & 0xFu) | ((sh & 3u) << 4)) - 32, s1 = (int) ((sl >> 4) | ((sh >> 2) << 4)) - 32;
+        const uint32_t qv[8] = {r.q0.x, r.q0.y, r.q0.z, r.q0.w, r.q1.x, r.q1.y, r.q1.z, r.q1.w};
+        uint32_t lo[8], hi[8];  // table bytes of values 4k .. 4k + 3 and 16 + 4k .. of sub-block 2j (k < 4) and 2j + 1 (k >= 4)
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            lo[k] = iq4nl_bytes(qv[k] & 0x0F0F0F0Fu);
+            hi[k] = iq4nl_bytes((qv[k] >> 4) & 0x0F0F0F0Fu);
+        }
+#pragma unroll
+        for (int col = 0; col < NC; ++col) {
+            const act * yb = y + (size_t) col * nblk + b;
+            const uint4 * yq = (const uint4 *) (yb->qs + 64 * j);
+            const uint4 y0 = yq[0], y1 = yq[1], y2 = yq[2], y3 = yq[3];
+            const uint32_t ya[8] = {y0.x, y0.y, y0.z, y0.w, y2.x, y2.y, y2.z, y2.w};  // values 0 .. 15 of the two sub-blocks
+            const uint32_t yb2[8] = {y1.x, y1.y, y1.z, y1.w, y3.x, y3.y, y3.z, y3.w};  // values 16 .. 31
+            int sa = 0, sb = 0;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                sa = dot4((int) lo[k], (int) ya[k], sa);
+                sa = dot4((int) hi[k], (int) yb2[k], sa);
+                sb = dot4((int) lo[4 + k], (int) ya[4 + k], sb);
+                sb = dot4((int) hi[4 + k], (int) yb2[4 + k], sb);
+            }
+            const int isum = __mul24(s0, sa) + __mul24(s1, sb);
+            acc[col] += (d * yb->d) * (float) isum;
+        }
+    }
+};
+
 // ------------------------------------------------------------------------------------------------ Q8_0
 struct T_Q80 {
     typedef q80_dev act;

@@ -391,6 +391,16 @@ __device__ __forceinline__ float dequant_elem(const int type, const uint8_t * __
             const float dl = h2f(ld16(b + 108)) * (float) s;
             return dl * (float) q;
         }
+        case GGML_TYPE_IQ4_XS: {
+            // {d, scales_h, scales_l[4], qs[128]}: value 32 ib + j is the low (j < 16) or high nibble of qs[16 ib + (j & 15)] through the IQ4_NL table; six-bit
+            // scale = nibble ib of scales_l | bit pair ib of scales_h << 4, used as ls - 32; y = (d * (ls - 32)) * table value, the two products rounded separately
+            const uint8_t * b = row + (i >> 8) * 136;
+            const int e = (int) (i & 255), ib = e >> 5, j = e & 31;
+            const int ls = ((b[4 + (ib >> 1)] >> (4 * (ib & 1))) & 0xF) | ((((int) ld16(b + 2) >> (2 * ib)) & 3) << 4);
+            const int c = b[8 + 16 * ib + (j & 15)];
+            const float dl = h2f(ld16(b)) * (float) (ls - 32);
+            return dl * (float) k_iq4nl_values[j < 16 ? (c & 0xF) : (c >> 4)];
+        }
         case GGML_TYPE_Q4_0: case GGML_TYPE_Q4_1: case GGML_TYPE_Q5_0: case GGML_TYPE_Q5_1: case GGML_TYPE_IQ4_NL: {
             // dequantize_row_* through the octet helpers the KV cache in these formats is read with (kv_dequant.h): level * d (+ m), one rounding an operation
             const char * b = (const char *) row + (i >> 5) * kv_block_bytes_any(type);

@@ -78,6 +78,7 @@ const char * ggml_type_name(enum ggml_type type) {
         case GGML_TYPE_Q2_K: return "q2_K";
         case GGML_TYPE_Q3_K: return "q3_K";
         case GGML_TYPE_Q4_K: return "q4_K";
+        case GGML_TYPE_IQ4_XS: return "iq4_xs";
         case GGML_TYPE_Q5_K: return "q5_K";
         case GGML_TYPE_Q6_K: return "q6_K";
         case GGML_TYPE_Q8_K: return "q8_K";

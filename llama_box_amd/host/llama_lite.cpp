@@ -167,6 +167,22 @@ static void synth_block(ggml_type type, uint64_t key, int64_t K, float wscale, u
             for (int k = 0; k < 4; ++k) b->scales[8 + k] = (uint8_t) ((L[k] >> 4) | ((L[k + 4] >> 4) << 2) | ((L[k + 8] >> 4) << 4) | ((L[k + 12] >> 4) << 6));
             b->d = f32_to_f16(scale * rk / 48.5f);
         } break;
+        case GGML_TYPE_IQ4_XS: {
+            // {d, scales_h, scales_l[4], qs[128]}: every field over its whole range — codes uniform in 0 .. 15 (table rms 67.4, mean -6), six-bit scales uniform
+            // in 0 .. 63, used as ls - 32 (rms 18.5, either sign), so the values are ~zero-mean; std ~ d * rms(ls - 32) * rms(table) = d * 18.5 * 67.4
+            block_iq4_xs * b = (block_iq4_xs *) out;
+            const uint64_t r = splitmix64(s);  // bits 6 ib .. 6 ib + 5 = ls of sub-block ib
+            uint32_t sl = 0, sh = 0;
+            for (int ib = 0; ib < 8; ++ib) {
+                const uint32_t ls = (uint32_t) (r >> (6 * ib)) & 63u;
+                sl |= (ls & 0xFu) << (4 * ib);
+                sh |= (ls >> 4) << (2 * ib);
+            }
+            b->scales_h = (uint16_t) sh;
+            for (int k = 0; k < 4; ++k) b->scales_l[k] = (uint8_t) (sl >> (8 * k));
+            fill(b->qs, 128);
+            b->d = f32_to_f16(scale * rk / 1246.0f);
+        } break;
         default: LLM_ASSERT(!"synth_block: unsupported type");
     }
 }
@@ -250,6 +266,19 @@ static void block_values(ggml_type type, const uint8_t * p, float * y) {
                 const int sc = ((is < 8 ? b->scales[is] & 0xF : b->scales[is - 8] >> 4) | (((b->scales[8 + (is & 3)] >> (2 * (is >> 2))) & 3) << 4)) - 32;
                 const int q = (int) ((b->qs[32 * n + l] >> (2 * j)) & 3) - (((b->hmask[l] >> (4 * n + j)) & 1) ? 0 : 4);
                 y[i] = d * (float) sc * (float) q;
+            }
+        } break;
+        case GGML_TYPE_IQ4_XS: {
+            static const int8_t iq4nl[16] = {-127, -104, -83, -65, -49, -35, -22, -10, 1, 13, 25, 38, 53, 69, 89, 113};
+            const block_iq4_xs * b = (const block_iq4_xs *) p;
+            const float d = f16_to_f32(b->d);
+            for (int ib = 0; ib < 8; ++ib) {
+                const int ls = ((b->scales_l[ib / 2] >> (4 * (ib % 2))) & 0xF) | (((b->scales_h >> (2 * ib)) & 3) << 4);
+                const float dl = d * (float) (ls - 32);
+                for (int j = 0; j < 16; ++j) {
+                    y[32 * ib + j] = dl * (float) iq4nl[b->qs[16 * ib + j] & 0xF];
+                    y[32 * ib + 16 + j] = dl * (float) iq4nl[b->qs[16 * ib + j] >> 4];
+                }
             }
         } break;
         case GGML_TYPE_Q4_0: case GGML_TYPE_Q4_1: case GGML_TYPE_Q5_0: case GGML_TYPE_Q5_1: case GGML_TYPE_IQ4_NL: {  // the 32 values of one block
@@ -435,6 +464,8 @@ extern "C" int llm_preset(const char * name, struct llm_hparams * hp) {
     else if (n == "test-llama-kq23") set("llama", 3, 256, 4, 2, 64, 512, 512, 512, 10000.0f, 1e-5f, 0, 0, LLM_FTYPE_MIXED_KQ23);
     else if (n == "llama3-8b-q3_k_m") set("llama", 32, 4096, 32, 8, 128, 14336, 128256, 8192, 500000.0f, 1e-5f, 0, 0, LLM_FTYPE_Q3_K_M);
     else if (n == "llama3-70b-q2_k") set("llama", 80, 8192, 64, 8, 128, 28672, 128256, 8192, 500000.0f, 1e-5f, 0, 0, LLM_FTYPE_Q2_K);
+    else if (n == "test-llama-iq4xs") set("llama", 3, 256, 4, 2, 64, 512, 512, 512, 10000.0f, 1e-5f, 0, 0, LLM_FTYPE_MIXED_IQ4XS);
+    else if (n == "llama3-8b-iq4_xs") set("llama", 32, 4096, 32, 8, 128, 14336, 128256, 8192, 500000.0f, 1e-5f, 0, 0, LLM_FTYPE_IQ4_XS);
     else if (n == "test-qwen2") set("qwen2", 2, 256, 4, 2, 64, 768, 768, 512, 1000000.0f, 1e-6f, GGML_ROPE_TYPE_NEOX, 1, LLM_FTYPE_MIXED);
     // models stored in bf16 (*-BF16.gguf: every matrix, token_embd and output in bf16; norms and biases f32)
     else if (n == "test-llama-bf16") set("llama", 3, 256, 4, 2, 64, 512, 512, 512, 10000.0f, 1e-5f, 0, 0, LLM_FTYPE_BF16);
@@ -535,6 +566,21 @@ static ggml_type pick_type(const llm_hparams & hp, const char * what, int il) {
             unsigned h = (unsigned) il * 7u;
             for (char c : w) h = h * 31u + (unsigned char) c;
             return cyc[h % 4];
+        }
+        // (recalled, not verified, as the two above; a tensor whose rows are no multiple of 256 would fall back to IQ4_NL — none of the presets has one)
+        case LLM_FTYPE_IQ4_XS:
+            if (w == "output") return GGML_TYPE_Q6_K;
+            if (w == "attn_v" || w == "ffn_down") return more ? GGML_TYPE_Q5_K : GGML_TYPE_IQ4_XS;
+            return GGML_TYPE_IQ4_XS;
+        case LLM_FTYPE_MIXED_IQ4XS: {
+            // format (tensor's place in the list + layer) mod 4: layer 0 has gate IQ4_XS and up forced to it (the SwiGLU stream form), layers 1 and 2 have
+            // gate and up in different formats; every role but attn_k meets IQ4_XS in some layer; output is Q6_K
+            static const ggml_type cyc[4] = {GGML_TYPE_IQ4_XS, GGML_TYPE_IQ4_NL, GGML_TYPE_Q4_K, GGML_TYPE_Q6_K};
+            static const char * const order[8] = {"attn_q", "attn_k", "attn_v", "attn_output", "ffn_gate", "ffn_up", "ffn_down", "output"};
+            if (w == "token_embd" || (w == "ffn_up" && il == 0)) return GGML_TYPE_IQ4_XS;
+            for (int k = 0; k < 8; ++k) if (w == order[k]) return cyc[(k + il) % 4];
+            LLM_ASSERT(!"pick_type: unknown tensor role");
+            return GGML_TYPE_IQ4_XS;
         }
         default: return GGML_TYPE_Q8_0;
     }

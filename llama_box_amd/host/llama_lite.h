@@ -38,6 +38,9 @@ enum llm_ftype {
     LLM_FTYPE_Q3_K_S = 14,       /* everything Q3_K, output Q6_K */
     LLM_FTYPE_MIXED_KQ23 = 15,   /* test recipe: cycles Q3_K/Q2_K/Q4_K/Q6_K over the tensors of one tiny model */
     LLM_FTYPE_BF16 = 16,         /* every matrix, token_embd and output BF16 (norms and biases F32), as a *-BF16.gguf holds a model */
+    /* IQ4_NL's table under a K-quant frame (the mix is recalled from llama.cpp's quantiser, not verified against it) */
+    LLM_FTYPE_IQ4_XS = 17,       /* IQ4_XS base, token_embd included; attn_v and ffn_down Q5_K in the "more bits" layers; output Q6_K */
+    LLM_FTYPE_MIXED_IQ4XS = 18,  /* test recipe: cycles IQ4_XS/IQ4_NL/Q4_K/Q6_K over the tensors of one tiny model; token_embd and layer 0's gate and up IQ4_XS */
 };
 
 struct llm_hparams {

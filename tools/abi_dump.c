@@ -160,6 +160,7 @@ int main(void) {
     SZ(block_q2_K); OFF(block_q2_K, scales); OFF(block_q2_K, qs); OFF(block_q2_K, d); OFF(block_q2_K, dmin);
     SZ(block_q3_K); OFF(block_q3_K, hmask); OFF(block_q3_K, qs); OFF(block_q3_K, scales); OFF(block_q3_K, d);
     SZ(block_q4_K); OFF(block_q4_K, scales); OFF(block_q4_K, qs);
+    SZ(block_iq4_xs); OFF(block_iq4_xs, d); OFF(block_iq4_xs, scales_h); OFF(block_iq4_xs, scales_l); OFF(block_iq4_xs, qs);
     SZ(block_q5_K); OFF(block_q5_K, scales); OFF(block_q5_K, qh); OFF(block_q5_K, qs);
     SZ(block_q6_K); OFF(block_q6_K, ql); OFF(block_q6_K, qh); OFF(block_q6_K, scales); OFF(block_q6_K, d);
     SZ(block_q8_K); OFF(block_q8_K, d); OFF(block_q8_K, qs); OFF(block_q8_K, bsums);
