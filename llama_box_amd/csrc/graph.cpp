@@ -18,9 +18,53 @@ namespace mi355x {
 
 static bool is_kq23_type(int t) { return t == GGML_TYPE_Q2_K || t == GGML_TYPE_Q3_K; }
 static bool is_iq4xs_type(int t) { return t == GGML_TYPE_IQ4_XS; }
-static bool is_quant(int t) { return t == GGML_TYPE_Q4_K || t == GGML_TYPE_Q5_K || t == GGML_TYPE_Q6_K || t == GGML_TYPE_Q8_0 || is_l32_type(t) || is_kq23_type(t) || is_iq4xs_type(t); }
+// what this file knows of a quantised weight type, one row per type: a new format is a new row here (and its hand-over in mmq_min_cols_for)
+struct wtype_info {
+    int type;
+    const char * tag;  // timing classes
+    int act;           // the reference's vec_dot_type: Q8_0 blocks for Q8_0 / Q4_0 / Q5_0 / IQ4_NL weights (one quantised row serves them all), Q8_1 for Q4_1 / Q5_1, Q8_K for the K-quants
+    int align;         // the block alignment l32_layout_ok asks of a matrix (0: the format is accepted without that check)
+    bool prologue;     // the mat-vec kernels have the norm / f32 / attention-partials prologue for it (Q8_0: for rows of whole 256-element groups, has_mmvq_prologue)
+};
+static const wtype_info k_wtypes[] = {
+    {GGML_TYPE_Q4_K, "q4_K", GGML_TYPE_Q8_K, 0, true},
+    {GGML_TYPE_Q5_K, "q5_K", GGML_TYPE_Q8_K, 0, true},
+    {GGML_TYPE_Q6_K, "q6_K", GGML_TYPE_Q8_K, 0, true},
+    {GGML_TYPE_Q8_0, "q8_0", GGML_TYPE_Q8_0, 0, true},
+    {GGML_TYPE_Q4_0, "q4_0", GGML_TYPE_Q8_0, 2, false},
+    {GGML_TYPE_Q4_1, "q4_1", GGML_TYPE_Q8_1, 4, false},
+    {GGML_TYPE_Q5_0, "q5_0", GGML_TYPE_Q8_0, 2, false},
+    {GGML_TYPE_Q5_1, "q5_1", GGML_TYPE_Q8_1, 4, false},
+    {GGML_TYPE_IQ4_NL, "iq4_nl", GGML_TYPE_Q8_0, 2, false},
+    {GGML_TYPE_Q2_K, "q2_K", GGML_TYPE_Q8_K, 4, true},
+    {GGML_TYPE_Q3_K, "q3_K", GGML_TYPE_Q8_K, 2, true},
+    {GGML_TYPE_IQ4_XS, "iq4_xs", GGML_TYPE_Q8_K, 8, true},
+};
+static const wtype_info * wtype_row(int t) {
+    for (const wtype_info & r : k_wtypes)
+        if (r.type == t) return &r;
+    return nullptr;
+}
+static bool is_quant(int t) { return wtype_row(t) != nullptr; }
 // the formats whose acceptance goes through l32_layout_ok
-static bool needs_layout_check(int t) { return is_l32_type(t) || is_kq23_type(t) || is_iq4xs_type(t); }
+static bool needs_layout_check(int t) {
+    const wtype_info * r = wtype_row(t);
+    return r && r->align != 0;
+}
+// (any other type: Q8_K, as before the table.  Every caller passes a quantised weight type or a panel kind, which is a row's act itself)
+static int act_kind(int wtype) {
+    const wtype_info * r = wtype_row(wtype);
+    return r ? r->act : GGML_TYPE_Q8_K;
+}
+static const char * type_tag(int t) {
+    const wtype_info * r = wtype_row(t);
+    return r ? r->tag : (t == GGML_TYPE_BF16 ? "bf16" : "f");
+}
+static bool has_mmvq_prologue(int t, int64_t K) {
+    const wtype_info * r = wtype_row(t);
+    return r && r->prologue && (t != GGML_TYPE_Q8_0 || (K % 256) == 0);
+}
+static bool weight_is_rowpar(const ggml_tensor * w) { return buffer_is_rowpar(w->view_src ? w->view_src->buffer : w->buffer); }
 // what the kernels over those formats assume of a matrix beyond contiguous rows: every block starts at the format's own alignment (2 bytes; 4 for the offset
 // formats, whose blocks are 20 / 24 bytes) — base address (null while the loader probes a type with a plain tensor: any real allocation is aligned), row and
 // matrix strides.  Their weights live in ordinary device buffers only: the split (-sm row) and row-parallel buffer types keep refusing them.
@@ -28,9 +72,10 @@ static bool needs_layout_check(int t) { return is_l32_type(t) || is_kq23_type(t)
 // (IQ4_XS too, at 8 bytes: its 136 = 8 * 17 byte blocks are read as one aligned 8-byte header and 16-byte pieces at 8 mod 16 — what every whole-block view of an
 // aligned allocation has)
 static bool l32_layout_ok(const ggml_tensor * a) {
-    const size_t al = is_iq4xs_type(a->type) ? 8 : ((a->type == GGML_TYPE_Q4_1 || a->type == GGML_TYPE_Q5_1 || a->type == GGML_TYPE_Q2_K) ? 4 : 2);
+    const wtype_info * r = wtype_row(a->type);
+    const size_t al = r && r->align ? (size_t) r->align : 2;  // (callers ask needs_layout_check first; any other type is held to 2 bytes, as before the table)
     if ((((uintptr_t) a->data) % al) || (a->nb[1] % al) || (a->nb[2] % al) || (a->nb[3] % al)) return false;
-    return !buffer_is_rowpar(a->view_src ? a->view_src->buffer : a->buffer) && !buffer_is_split(a->buffer);
+    return !weight_is_rowpar(a) && !buffer_is_split(a->buffer);
 }
 // batches at least this wide run on the matrix cores.  The option's default (3) is per weight type since round 6: Q4_K / Q6_K matrices take the weight-streaming
 // kernel from TWO columns on (a 2-sequence step of Llama-3-8B Q4_K_M: 2.89-3.03 -> 2.78 ms — the multi-column mat-vec path has none of the batch path's fusions,
@@ -45,16 +90,66 @@ static inline int mmq_min_cols_for(const backend_ctx * c, int wtype) {
     if (c->opt.mmq_min_cols != 3) return c->opt.mmq_min_cols;
     return (wtype == GGML_TYPE_Q4_K || (wtype == GGML_TYPE_Q6_K && !c->mm_q5_major)) ? 2 : 3;
 }
-// the reference's vec_dot_type: Q8_0 blocks for Q8_0 / Q4_0 / Q5_0 / IQ4_NL weights (one quantised row serves them all), Q8_1 for Q4_1 / Q5_1, Q8_K for the K-quants
-static int act_kind(int wtype) {
-    if (wtype == GGML_TYPE_Q4_1 || wtype == GGML_TYPE_Q5_1) return GGML_TYPE_Q8_1;
-    return (wtype == GGML_TYPE_Q8_0 || is_l32_type(wtype)) ? GGML_TYPE_Q8_0 : GGML_TYPE_Q8_K;
+// which kernel family serves a quantised MUL_MAT of M columns over the matrix w — asked by run_mul_mat_q, which launches it, and by run_node, which decides from it
+// which neighbours (siblings, ADDs) the launch may take along.  The `supported` tests each refuse every type but their own, so their order decides nothing
+// between formats; within Q8_0 the weight-streaming form goes first.
+enum mm_kind {
+    MM_VEC,         // passes of the mat-vec kernel over <= 8 columns each (mmvq.hip)
+    MM_L32,         // Q4_0 .. IQ4_NL, 9 columns and more: the integer matrix cores (mmq_q80.hip with the format's staging step), never passes of the mat-vec kernel
+    MM_Q80_SKINNY,  // Q8_0, 9 .. 128 columns: the weight-streaming matrix-core kernel
+    MM_Q80_GEMM,    // Q8_0 prompt batches: the tiled kernel
+    MM_I8,          // K-quants and IQ4_XS on the int8 matrix cores (mmq_i8.hip: skinny, wide or tiled form)
+    MM_F16,         // Q4_K / Q5_K / Q6_K on the f16 tiles of mmq.hip (option mmq_i8 = 0)
+};
+struct mm_form {
+    mm_kind kind;
+    int l32;  // MM_L32: mmq_l32_form's 1 (9 .. 128 columns, activations in panel order) or 2
+};
+static mm_form batch_form(const backend_ctx * c, const ggml_tensor * w, int64_t M) {
+    const int64_t K = w->ne[0], N = w->ne[1];
+    if (const int l32 = mmq_l32_form(w->type, K, N, M)) return {MM_L32, l32};
+    if (mmq_q80_skinny_supported(w->type, K, N, M)) return {MM_Q80_SKINNY, 0};
+    if (M >= c->opt.q80_min_cols && mmq_q80_supported(w->type, K, N, M)) return {MM_Q80_GEMM, 0};
+    if (M >= mmq_min_cols_for(c, w->type)) {
+        if (c->opt.mmq_i8 && mmq_i8_supported(w->type, K, N, M)) return {MM_I8, 0};
+        if (mmq_supported(w->type, K, N, M)) return {MM_F16, 0};
+    }
+    return {MM_VEC, 0};
 }
 static bool is_f32_contig(const ggml_tensor * t) { return t->type == GGML_TYPE_F32 && ggml_abi_is_contiguous(t); }
 static bool rows_contig(const ggml_tensor * t) { return t->nb[0] == ggml_abi_type_size(t->type); }
 static bool same_shape(const ggml_tensor * a, const ggml_tensor * b) {
     for (int i = 0; i < 4; ++i) if (a->ne[i] != b->ne[i]) return false;
     return true;
+}
+static bool is_view_op(const ggml_tensor * t) {
+    return t->op == GGML_OP_NONE || t->op == GGML_OP_VIEW || t->op == GGML_OP_RESHAPE || t->op == GGML_OP_PERMUTE || t->op == GGML_OP_TRANSPOSE;
+}
+static const ggml_tensor * through_views(const ggml_tensor * t) {
+    while (t && (t->op == GGML_OP_RESHAPE || t->op == GGML_OP_VIEW) && t->src[0] && t->data == t->src[0]->data) t = t->src[0];
+    return t;
+}
+static bool ranges_overlap(const ggml_tensor * x, const ggml_tensor * y) {
+    if (!x->data || !y->data) return false;
+    const char * x0 = (const char *) x->data, * y0 = (const char *) y->data;
+    return x0 < y0 + ggml_abi_nbytes(y) && y0 < x0 + ggml_abi_nbytes(x);
+}
+// the row stride, in floats, of the bias row (0: every column adds the same row) or residual that rides in a mat-mul's store
+static int64_t addend_stride(const ggml_tensor * add) { return (!add || ggml_abi_nrows(add) == 1) ? 0 : (int64_t) (add->nb[1] / 4); }
+// (value-initialised: ensure_rope_table compares these with memcmp.  The fused launches serve no ggml_rope_multi and leave the sections zero)
+static rope_params rope_params_of(const ggml_tensor * rope, bool keep_sections) {
+    rope_params p{};
+    p.n_dims = rope->op_params[1];
+    p.mode = rope->op_params[2];
+    p.n_ctx_orig = rope->op_params[4];
+    p.freq_base = ggml_abi_op_param_f32(rope, 5);
+    p.freq_scale = ggml_abi_op_param_f32(rope, 6);
+    p.ext_factor = ggml_abi_op_param_f32(rope, 7);
+    p.attn_factor = ggml_abi_op_param_f32(rope, 8);
+    p.beta_fast = ggml_abi_op_param_f32(rope, 9);
+    p.beta_slow = ggml_abi_op_param_f32(rope, 10);
+    if (keep_sections) memcpy(p.sections, rope->op_params + 11, sizeof(p.sections));
+    return p;
 }
 
 // ------------------------------------------------------------------------------------------------ supports_op
@@ -77,6 +172,9 @@ static bool mm_cache_image_ok(const ggml_tensor * op) {
     if (a->nb[0] != ggml_abi_type_size(a->type) || (a->ne[0] % 32) != 0 || (a->nb[1] % 2) || (a->nb[2] % 2) || a->ne[3] != 1 || b->ne[3] != 1 || b->nb[0] != 4) return false;
     return a->ne[2] > 0 && b->ne[2] % a->ne[2] == 0;
 }
+// ... and this MUL_MAT node runs that way.  run_node asks this before it looks at src0's type, and so must plan_ws: a Q8_0 cache VIEW taken for a quantised weight
+// there, the image of a large view was written past the end of the scratch
+static bool mm_runs_on_image(const ggml_tensor * n) { return mm_cache_image_ok(n) && !buffer_is_split(n->src[0]->buffer); }
 
 // which attention path serves this FLASH_ATTN_EXT node: 0 none (the host keeps it on the CPU backend), 1 the f16 kernels on the cache views in place,
 // 2 the lane-parallel kernel on block_q8_0 K / V, 3 the f16 kernels on an f16 IMAGE of whichever of K / V is kept in another type (kv_types.hip:
@@ -133,7 +231,7 @@ static bool mm_id_ok(const ggml_tensor * op) {
     if (!a || !b || !ids || b->type != GGML_TYPE_F32 || ids->type != GGML_TYPE_I32 || op->type != GGML_TYPE_F32 || !ggml_abi_is_contiguous(op)) return false;
     if (!(is_quant(a->type) || a->type == GGML_TYPE_F16 || a->type == GGML_TYPE_BF16 || a->type == GGML_TYPE_F32) || !rows_contig(a) || a->ne[3] != 1 || a->ne[0] % ggml_abi_blck_size(a->type) != 0) return false;
     if (needs_layout_check(a->type) && !l32_layout_ok(a)) return false;
-    if (buffer_is_rowpar(a->view_src ? a->view_src->buffer : a->buffer)) return false;  // (row-parallel weights hold a slice of every row: MUL_MAT only)
+    if (weight_is_rowpar(a)) return false;  // (row-parallel weights hold a slice of every row: MUL_MAT only)
     if (b->ne[0] != a->ne[0] || b->nb[0] != 4 || b->ne[3] != 1 || (b->nb[1] % 4) || (b->nb[2] % 4)) return false;
     if (ids->nb[0] != 4 || (ids->nb[1] % 4) || ids->ne[2] != 1 || ids->ne[3] != 1 || ids->ne[1] != b->ne[2] || ids->ne[0] < 1 || ids->ne[1] < 1) return false;
     if (b->ne[1] != 1 && b->ne[1] != ids->ne[0]) return false;
@@ -277,9 +375,7 @@ static ws_plan plan_ws(backend_ctx * c, const ggml_cgraph * g) {
     }
     for (int i = 0; i < g->n_nodes; ++i) {
         const ggml_tensor * n = g->nodes[i];
-        // (a Q8_0 cache VIEW is served through its f16 image — run_node asks mm_cache_image_ok first, so must this: taken for a quantised weight here, the image
-        // of a large view was written past the end of the scratch)
-        const bool mm_image = n->op == GGML_OP_MUL_MAT && mm_cache_image_ok(n) && !buffer_is_split(n->src[0]->buffer);
+        const bool mm_image = n->op == GGML_OP_MUL_MAT && mm_runs_on_image(n);
         if (n->op == GGML_OP_MUL_MAT && is_quant(n->src[0]->type) && !mm_image) {
             const ggml_tensor * b = n->src[1];
             const int64_t Mc = b->ne[1] * b->ne[2] * b->ne[3];
@@ -493,29 +589,59 @@ static const void * quantized_src1(exec_state & st, const ggml_tensor * b, int w
     return dst;
 }
 
-static const char * type_tag(int t) {
-    switch (t) {
-        case GGML_TYPE_Q2_K: return "q2_K";
-        case GGML_TYPE_Q3_K: return "q3_K";
-        case GGML_TYPE_Q4_K: return "q4_K";
-        case GGML_TYPE_Q5_K: return "q5_K";
-        case GGML_TYPE_Q6_K: return "q6_K";
-        case GGML_TYPE_Q8_0: return "q8_0";
-        case GGML_TYPE_Q4_0: return "q4_0";
-        case GGML_TYPE_Q4_1: return "q4_1";
-        case GGML_TYPE_Q5_0: return "q5_0";
-        case GGML_TYPE_Q5_1: return "q5_1";
-        case GGML_TYPE_IQ4_NL: return "iq4_nl";
-        case GGML_TYPE_IQ4_XS: return "iq4_xs";
-        case GGML_TYPE_BF16: return "bf16";
-        default: return "f";
+// ------------------------------------------------------------------------------------------------ who reads a tensor
+// Walks the nodes from `from` on and asks admit(u, s) of every node u that reads t in slot s.  Returns the index of the last reader when every reader was
+// admitted and they are ALL of t's readers (use_count: a reader may sit in another backend's split); -1 otherwise.
+template <class Admit>
+static int last_reader_if_all(const exec_state & st, int from, const ggml_tensor * t, Admit && admit) {
+    const ggml_cgraph * g = st.g;
+    int last = -1, n_cons = 0;
+    for (int j = from; j < g->n_nodes; ++j) {
+        const ggml_tensor * u = g->nodes[j];
+        for (int s = 0; s < GGML_MAX_SRC; ++s) {
+            if (u->src[s] != t) continue;
+            if (!admit(u, s)) return -1;
+            last = j;
+            n_cons++;
+        }
     }
+    return (n_cons != 0 && n_cons == use_count(st, t)) ? last : -1;
+}
+// t's quantised blocks were left in the activation area by the node at `at`; the area is shared: no other quantised mat-mul (which would overwrite it) and no
+// MUL_MAT_ID may run before the last reader
+static bool act_area_kept_for(const exec_state & st, int at, int last, const ggml_tensor * t) {
+    for (int j = at + 1; j <= last; ++j) {
+        const ggml_tensor * u = st.g->nodes[j];
+        if (u->op == GGML_OP_MUL_MAT && is_quant(u->src[0]->type) && u->src[1] != t) return false;
+        if (u->op == GGML_OP_MUL_MAT_ID) return false;
+    }
+    return true;
+}
+// Batches (M > 1): may the producer of `t` (node index `at`) write ONLY the Q8_K blocks of its result into the activation
+// scratch?  Yes when every use of t is src1 of a K-quant MUL_MAT and no other quantised mat-mul (which would overwrite the
+// scratch) runs before the last of them.
+static bool quant_consumers_only(const exec_state & st, int at, const ggml_tensor * t) {
+    if ((t->flags & GGML_TENSOR_FLAG_OUTPUT) || t->type != GGML_TYPE_F32 || (t->ne[0] % 256) != 0 || t->ne[0] > 16384 * 4) return false;
+    const int last = last_reader_if_all(st, at + 1, t, [&](const ggml_tensor * u, int s) {
+        const ggml_tensor * wt = u->src[0];
+        return u->op == GGML_OP_MUL_MAT && s == 1 && (wt->type == GGML_TYPE_Q4_K || wt->type == GGML_TYPE_Q5_K || wt->type == GGML_TYPE_Q6_K) &&
+               !buffer_is_split(wt->buffer);  // (split weights read the f32 activations on other devices: the tensor itself must exist)
+    });
+    return last >= 0 && act_area_kept_for(st, at, last, t);
+}
+// ... and the same question for Q8_0 weights (round 6): every reader of t is a Q8_0 mat-mul that takes the 9 .. 128-column matrix-core kernel (its activations in panel
+// order), so a producer may leave Q8_0 panel blocks instead of f32
+static bool q80_panel_consumers_only(const exec_state & st, int at, const ggml_tensor * t) {
+    if ((t->flags & GGML_TENSOR_FLAG_OUTPUT) || t->type != GGML_TYPE_F32 || (t->ne[0] % 128) != 0) return false;
+    const int64_t M = ggml_abi_nrows(t);
+    const int last = last_reader_if_all(st, at + 1, t, [&](const ggml_tensor * u, int s) {
+        const ggml_tensor * wt = u->src[0];
+        return u->op == GGML_OP_MUL_MAT && s == 1 && wt->type == GGML_TYPE_Q8_0 && wt->ne[2] == 1 && wt->ne[3] == 1 && rows_contig(wt) && !buffer_is_split(wt->buffer) &&
+               mmq_q80_skinny_supported(wt->type, wt->ne[0], wt->ne[1], M) && u->type == GGML_TYPE_F32 && ggml_abi_is_contiguous(u) && !(tp_active(st.c) && weight_is_rowpar(wt));
+    });
+    return last >= 0 && act_area_kept_for(st, at, last, t);
 }
 
-static bool is_view_op(const ggml_tensor * t);
-static bool ranges_overlap(const ggml_tensor * x, const ggml_tensor * y);
-static bool quant_consumers_only(const exec_state & st, int at, const ggml_tensor * t);
-static bool same_shape(const ggml_tensor * a, const ggml_tensor * b);
 // quantised mat-mul, optionally with fused epilogue; w2 != null -> SwiGLU over (w, w2)
 static bool run_mul_mat_q(exec_state & st, const ggml_tensor * w, const ggml_tensor * w2, const ggml_tensor * b, ggml_tensor * dst,
                           const ggml_tensor * add, const ggml_tensor * add2) {
@@ -523,7 +649,32 @@ static bool run_mul_mat_q(exec_state & st, const ggml_tensor * w, const ggml_ten
     const int64_t K = w->ne[0], N = w->ne[1];
     const int64_t M = b->ne[1] * b->ne[2] * b->ne[3];
     const double wbytes = (double) ggml_abi_row_size(w->type, K) * (double) N * (w2 ? 2.0 : 1.0);
-    const bool kquant = is_kq23_type(w->type) || is_iq4xs_type(w->type) || w->type == GGML_TYPE_Q4_K || w->type == GGML_TYPE_Q5_K || w->type == GGML_TYPE_Q6_K || (w->type == GGML_TYPE_Q8_0 && (K % 256) == 0);  // formats with the mat-vec prologue
+    const bool kquant = has_mmvq_prologue(w->type, K);
+    // what the prologue launch and the plain mat-vec passes at the end share (the decode copies are the plane-layout copies the streaming kernels read with
+    // non-temporal loads: backend.cpp, repack.hip)
+    auto mmvq_base = [&]() {
+        mmvq_args a{};
+        a.W = (const uint8_t *) w->data;
+        a.W2 = w2 ? (const uint8_t *) w2->data : nullptr;
+        a.w_nb1 = (int64_t) w->nb[1];
+        a.type = w->type;
+        a.K = (int) K;
+        a.N = (int) N;
+        a.ncols = (int) M;
+        if (M == 1) {
+            a.Wp = decode_copy(c, w);
+            a.W2p = w2 && a.Wp ? decode_copy(c, w2) : nullptr;
+            if (w2 && !a.W2p) a.Wp = nullptr;
+            c->st.decode_copy_launches += a.Wp != nullptr;
+        }
+        a.dst = (float *) dst->data;
+        a.dst_stride = (int64_t) (dst->nb[1] / 4);
+        a.add = add ? (const float *) add->data : nullptr;
+        a.add_stride = addend_stride(add);
+        a.add2 = add2 ? (const float *) add2->data : nullptr;
+        a.add2_stride = addend_stride(add2);
+        return a;
+    };
     auto dn = st.deferred.find(b);
     const bool pro_norm = dn != st.deferred.end();
     const bool pro_fa = st.fa_wo.b == b && st.fa_wo.part != nullptr;  // (set by the FLASH_ATTN_EXT node after checking this very mat-vec)
@@ -536,23 +687,12 @@ static bool run_mul_mat_q(exec_state & st, const ggml_tensor * w, const ggml_ten
         MI_ERR("graph_compute: attention partials were left for a mat-vec that cannot merge them");
         return false;
     }
+    if (pro_norm && M != 1) {  // (can_defer_norm admits one-row norms only; mmvq_base takes the decode copies for one column alone)
+        MI_ERR("graph_compute: a norm was deferred to a mat-mul of several columns");
+        return false;
+    }
     if (pro_norm || pro_f32 || pro_fa) {
-        mmvq_args a{};
-        a.W = (const uint8_t *) w->data;
-        a.W2 = w2 ? (const uint8_t *) w2->data : nullptr;
-        a.Wp = decode_copy(c, w);  // (the plane-layout copies the streaming kernels read with non-temporal loads: backend.cpp, repack.hip)
-        a.W2p = w2 && a.Wp ? decode_copy(c, w2) : nullptr;
-        if (w2 && !a.W2p) a.Wp = nullptr;
-        c->st.decode_copy_launches += a.Wp != nullptr;
-        a.w_nb1 = (int64_t) w->nb[1];
-        a.type = w->type;
-        a.K = (int) K;
-        a.N = (int) N;
-        a.ncols = 1;
-        a.dst = (float *) dst->data;
-        a.dst_stride = (int64_t) (dst->nb[1] / 4);
-        a.add = add ? (const float *) add->data : nullptr;
-        a.add2 = add2 ? (const float *) add2->data : nullptr;
+        mmvq_args a = mmvq_base();  // (one column: every prologue is admitted for M == 1 only — checked above — and a one-row addend has stride 0)
         a.x = pro_norm ? (const float *) dn->second.x->data : (pro_fa ? nullptr : (const float *) b->data);
         if (pro_fa) {
             a.fa_part = st.fa_wo.part;
@@ -593,54 +733,49 @@ static bool run_mul_mat_q(exec_state & st, const ggml_tensor * w, const ggml_ten
         c->st.kernel_launches++;
         return true;
     }
-    // Q4_0 .. IQ4_NL, 9 columns and more: the integer matrix cores (mmq_q80.hip with the format's staging step), never passes of the mat-vec kernel
-    const int l32_form = (is_l32_type(w->type) && !w2 && !add2) ? mmq_l32_form(w->type, K, N, M) : 0;
-    if (l32_form) {
+    // the matrix-core stores take ONE addend (the f16 tiles none) and no SwiGLU: what carries more keeps the mat-vec passes
+    mm_form form = batch_form(c, w, M);
+    if (w2 || add2 || (add && form.kind == MM_F16)) form = {MM_VEC, 0};
+    const float * addp = add ? (const float *) add->data : nullptr;
+    const int64_t add_stride = addend_stride(add);
+    float * const out = (float *) dst->data;
+    const int64_t out_stride = (int64_t) (dst->nb[1] / 4);
+    if (form.kind == MM_L32) {
         const bool one = act_kind(w->type) == GGML_TYPE_Q8_1;
         // (kinds as wtype: quantized_src1 maps a weight type through act_kind and takes a panel kind as it is)
-        const void * act = quantized_src1(st, b, l32_form == 1 ? (one ? MI_ACT_Q81_PANEL : MI_ACT_Q80_PANEL) : w->type);
-        timed_scope ts(c, (std::string("mmq_") + type_tag(w->type) + (l32_form == 1 ? "_skinny" : "")).c_str(), wbytes);
-        const int64_t arows = add ? add->ne[1] * add->ne[2] * add->ne[3] : 0;
-        launch_mmq_l32(c->stream, w->type, l32_form, (const uint8_t *) w->data, (int64_t) w->nb[1], (int) K, (int) N, (int) M, act, (float *) dst->data, (int64_t) (dst->nb[1] / 4),
-                       add ? (const float *) add->data : nullptr, (!add || arows == 1) ? 0 : (int64_t) (add->nb[1] / 4));
-        c->st.kernel_launches += l32_form == 1 ? (M + 31) / 32 : 1;
-        c->st.skinny_launches += l32_form == 1;
+        const void * act = quantized_src1(st, b, form.l32 == 1 ? (one ? MI_ACT_Q81_PANEL : MI_ACT_Q80_PANEL) : w->type);
+        timed_scope ts(c, (std::string("mmq_") + type_tag(w->type) + (form.l32 == 1 ? "_skinny" : "")).c_str(), wbytes);
+        launch_mmq_l32(c->stream, w->type, form.l32, (const uint8_t *) w->data, (int64_t) w->nb[1], (int) K, (int) N, (int) M, act, out, out_stride, addp, add_stride);
+        c->st.kernel_launches += form.l32 == 1 ? (M + 31) / 32 : 1;
+        c->st.skinny_launches += form.l32 == 1;
         return true;
     }
-    const bool q80_skinny = w->type == GGML_TYPE_Q8_0 && !w2 && !add2 && mmq_q80_skinny_supported(w->type, K, N, M);
     // the prompt GEMM over Q8_0 weights reads both operands in panel order when the weights have their panel copy (GGML_MI355X_Q80_GEMM_PANELS=0: as before round 6)
     static const bool gemm_panels = !getenv("GGML_MI355X_Q80_GEMM_PANELS") || atoi(getenv("GGML_MI355X_Q80_GEMM_PANELS")) != 0;
-    const bool q80_gemm = !q80_skinny && w->type == GGML_TYPE_Q8_0 && M >= c->opt.q80_min_cols && !w2 && !add2 && mmq_q80_supported(w->type, K, N, M);
-    const uint8_t * q80_gemm_wp = (q80_gemm && gemm_panels) ? q80_panel_copy(c, w) : nullptr;
-    const void * act = quantized_src1(st, b, (q80_skinny || q80_gemm_wp) ? MI_ACT_Q80_PANEL : w->type);
-    if (q80_skinny) {  // 9 .. 32 columns of a -np decode step (round 6)
+    const uint8_t * q80_gemm_wp = (form.kind == MM_Q80_GEMM && gemm_panels) ? q80_panel_copy(c, w) : nullptr;
+    const void * act = quantized_src1(st, b, (form.kind == MM_Q80_SKINNY || q80_gemm_wp) ? MI_ACT_Q80_PANEL : w->type);
+    if (form.kind == MM_Q80_SKINNY) {  // 9 .. 32 columns of a -np decode step (round 6)
         const uint8_t * wp = q80_panel_copy(c, w);
         c->st.decode_copy_launches += wp != nullptr;
         timed_scope ts(c, "mmq_q8_0_skinny", wbytes);
-        const int64_t arows = add ? add->ne[1] * add->ne[2] * add->ne[3] : 0;
-        launch_mmq_q80_skinny(c->stream, (const uint8_t *) w->data, wp, (int64_t) w->nb[1], (int) K, (int) N, (int) M, act, (float *) dst->data, (int64_t) (dst->nb[1] / 4),
-                              add ? (const float *) add->data : nullptr, (!add || arows == 1) ? 0 : (int64_t) (add->nb[1] / 4));
+        launch_mmq_q80_skinny(c->stream, (const uint8_t *) w->data, wp, (int64_t) w->nb[1], (int) K, (int) N, (int) M, act, out, out_stride, addp, add_stride);
         c->st.kernel_launches++;
         c->st.skinny_launches++;
         return true;
     }
-    if (q80_gemm) {
+    if (form.kind == MM_Q80_GEMM) {
         timed_scope ts(c, "mmq_q8_0", wbytes);
-        const int64_t arows = add ? add->ne[1] * add->ne[2] * add->ne[3] : 0;
         c->st.decode_copy_launches += q80_gemm_wp != nullptr;
-        launch_mmq_q80(c->stream, (const uint8_t *) w->data, q80_gemm_wp, (int64_t) w->nb[1], (int) K, (int) N, (int) M, act, (float *) dst->data, (int64_t) (dst->nb[1] / 4),
-                       add ? (const float *) add->data : nullptr, (!add || arows == 1) ? 0 : (int64_t) (add->nb[1] / 4));
+        launch_mmq_q80(c->stream, (const uint8_t *) w->data, q80_gemm_wp, (int64_t) w->nb[1], (int) K, (int) N, (int) M, act, out, out_stride, addp, add_stride);
         c->st.kernel_launches++;
         return true;
     }
-    const bool i8 = c->opt.mmq_i8 && mmq_i8_supported(w->type, K, N, M);
-    if (M >= mmq_min_cols_for(c, w->type) && !w2 && !add2 && (!add || i8) && (i8 || mmq_supported(w->type, K, N, M))) {
+    if (form.kind == MM_I8 || form.kind == MM_F16) {
+        const bool i8 = form.kind == MM_I8;
         timed_scope ts(c, (std::string("mmq_") + type_tag(w->type) + "_n" + std::to_string(N) + "_k" + std::to_string(K)).c_str(), wbytes, i8);
         const int ks = st.epi_dst == dst ? 1 : ((N % 4) == 0 && (dst->nb[1] % 16) == 0 ? mmq_pick_ksplit(K, N, M, c->opt.mmq_skinny, w->type) : 1);
         float * part = (float *) ((char *) c->ws + st.aux_off);
         if (i8) {
-            const int64_t arows = add ? add->ne[1] * add->ne[2] * add->ne[3] : 0;
-            const int64_t add_stride = (!add || arows == 1) ? 0 : (int64_t) (add->nb[1] / 4);
             // K split, and the next kernel is the RMS_NORM -> MUL -> Q8_K of exactly this result: it sums the partial products itself
             // (writing the f32 result on the way) — one launch instead of reduce + norm
             bool defer = false;
@@ -659,51 +794,27 @@ static bool run_mul_mat_q(exec_state & st, const ggml_tensor * w, const ggml_ten
                 }
             }
             const mmq_epi * epi = st.epi_dst == dst ? &st.epi : nullptr;
-            const int served = launch_mmq_i8(c->stream, w->type, (const uint8_t *) w->data, (int64_t) w->nb[1], (int) K, (int) N, (int) M, act, (float *) dst->data, (int64_t) (dst->nb[1] / 4), c->opt.mmq_bn, epi ? 1 : ks, part,
-                                             add ? (const float *) add->data : nullptr, add_stride, !defer, c->opt.mmq_skinny, epi);
+            const int served = launch_mmq_i8(c->stream, w->type, (const uint8_t *) w->data, (int64_t) w->nb[1], (int) K, (int) N, (int) M, act, out, out_stride, c->opt.mmq_bn, epi ? 1 : ks, part,
+                                             addp, add_stride, !defer, c->opt.mmq_skinny, epi);
             c->st.skinny_launches += served == 1;
             c->st.wide_launches += served == 2;
             c->st.tiled_launches += served == 0;
             if (defer) {
                 st.sk_dst = dst;
-                st.sk = splitk_src{part, ks, (int64_t) M * N, add ? (const float *) add->data : nullptr, add_stride, (float *) dst->data, (int64_t) (dst->nb[1] / 4)};
+                st.sk = splitk_src{part, ks, (int64_t) M * N, addp, add_stride, out, out_stride};
                 c->st.kernel_launches++;
                 st.sk_next = -1;
                 return true;
             }
         }
         else
-            launch_mmq(c->stream, w->type, (const uint8_t *) w->data, (int64_t) w->nb[1], (int) K, (int) N, (int) M, act, (float *) dst->data, (int64_t) (dst->nb[1] / 4), ks, part);
+            launch_mmq(c->stream, w->type, (const uint8_t *) w->data, (int64_t) w->nb[1], (int) K, (int) N, (int) M, act, out, out_stride, ks, part);
         if (ks > 1) c->st.kernel_launches++;
         c->st.kernel_launches++;
         return true;
     }
-    mmvq_args a{};
-    a.W = (const uint8_t *) w->data;
-    a.W2 = w2 ? (const uint8_t *) w2->data : nullptr;
-    a.w_nb1 = (int64_t) w->nb[1];
-    a.type = w->type;
-    a.K = (int) K;
-    a.N = (int) N;
-    a.ncols = (int) M;
+    mmvq_args a = mmvq_base();
     a.act = act;
-    if (M == 1) {
-        a.Wp = decode_copy(c, w);
-        a.W2p = w2 && a.Wp ? decode_copy(c, w2) : nullptr;
-        if (w2 && !a.W2p) a.Wp = nullptr;
-        c->st.decode_copy_launches += a.Wp != nullptr;
-    }
-    a.dst = (float *) dst->data;
-    a.dst_stride = (int64_t) (dst->nb[1] / 4);
-    auto addend = [&](const ggml_tensor * t, const float *& p, int64_t & stride) {
-        p = nullptr;
-        stride = 0;
-        if (!t) return;
-        p = (const float *) t->data;
-        stride = (t->ne[1] * t->ne[2] * t->ne[3] == 1) ? 0 : (int64_t) (t->nb[1] / 4);
-    };
-    addend(add, a.add, a.add_stride);
-    addend(add2, a.add2, a.add2_stride);
     const int rpw = (M == 1 && N >= 2048) ? 2 : 1;
     char cls[64];
     snprintf(cls, sizeof(cls), "mmvq_%s%s_nc%d", type_tag(w->type), w2 ? "_glu" : "", (int) std::min<int64_t>(M, 8));
@@ -730,62 +841,7 @@ static const ggml_tensor * add_partner(const ggml_tensor * add, const ggml_tenso
     return o;
 }
 
-// Batches (M > 1): may the producer of `t` (node index `at`) write ONLY the Q8_K blocks of its result into the activation
-// scratch?  Yes when every use of t is src1 of a K-quant MUL_MAT and no other quantised mat-mul (which would overwrite the
-// scratch) runs before the last of them.
-static bool quant_consumers_only(const exec_state & st, int at, const ggml_tensor * t) {
-    if ((t->flags & GGML_TENSOR_FLAG_OUTPUT) || t->type != GGML_TYPE_F32 || (t->ne[0] % 256) != 0 || t->ne[0] > 16384 * 4) return false;
-    const ggml_cgraph * g = st.g;
-    int last = -1, n_cons = 0;
-    for (int j = at + 1; j < g->n_nodes; ++j) {
-        const ggml_tensor * u = g->nodes[j];
-        for (int s = 0; s < GGML_MAX_SRC; ++s) {
-            if (u->src[s] != t) continue;
-            const ggml_tensor * wt = u->src[0];
-            if (!(u->op == GGML_OP_MUL_MAT && s == 1 && (wt->type == GGML_TYPE_Q4_K || wt->type == GGML_TYPE_Q5_K || wt->type == GGML_TYPE_Q6_K))) return false;
-            if (buffer_is_split(wt->buffer)) return false;  // (split weights read the f32 activations on other devices: the tensor itself must exist)
-            last = j;
-            n_cons++;
-        }
-    }
-    if (n_cons == 0 || n_cons != use_count(st, t)) return false;
-    for (int j = at + 1; j <= last; ++j) {
-        const ggml_tensor * u = g->nodes[j];
-        if (u->op == GGML_OP_MUL_MAT && is_quant(u->src[0]->type) && u->src[1] != t) return false;
-        if (u->op == GGML_OP_MUL_MAT_ID) return false;
-    }
-    return true;
-}
-// ... and the same question for Q8_0 weights (round 6): every reader of t is a Q8_0 mat-mul that takes the 9 .. 128-column matrix-core kernel (its activations in panel
-// order), so a producer may leave Q8_0 panel blocks instead of f32
-static bool q80_panel_consumers_only(const exec_state & st, int at, const ggml_tensor * t) {
-    if ((t->flags & GGML_TENSOR_FLAG_OUTPUT) || t->type != GGML_TYPE_F32 || (t->ne[0] % 128) != 0) return false;
-    const int64_t M = t->ne[1] * t->ne[2] * t->ne[3];
-    const ggml_cgraph * g = st.g;
-    int last = -1, n_cons = 0;
-    for (int j = at + 1; j < g->n_nodes; ++j) {
-        const ggml_tensor * u = g->nodes[j];
-        for (int s = 0; s < GGML_MAX_SRC; ++s) {
-            if (u->src[s] != t) continue;
-            const ggml_tensor * wt = u->src[0];
-            if (!(u->op == GGML_OP_MUL_MAT && s == 1 && wt->type == GGML_TYPE_Q8_0 && wt->ne[2] == 1 && wt->ne[3] == 1 && rows_contig(wt) && !buffer_is_split(wt->buffer) &&
-                  mmq_q80_skinny_supported(wt->type, wt->ne[0], wt->ne[1], M) && u->type == GGML_TYPE_F32 && ggml_abi_is_contiguous(u)))
-                return false;
-            if (tp_active(st.c) && buffer_is_rowpar(wt->view_src ? wt->view_src->buffer : wt->buffer)) return false;
-            last = j;
-            n_cons++;
-        }
-    }
-    if (n_cons == 0 || n_cons != use_count(st, t)) return false;
-    for (int j = at + 1; j <= last; ++j) {  // (the activation area is shared: no other quantised mat-mul may run before the last reader)
-        const ggml_tensor * u = g->nodes[j];
-        if (u->op == GGML_OP_MUL_MAT && is_quant(u->src[0]->type) && u->src[1] != t) return false;
-        if (u->op == GGML_OP_MUL_MAT_ID) return false;
-    }
-    return true;
-}
-static void mark_q8_cache(exec_state & st, const ggml_tensor * t, int kind = GGML_TYPE_Q8_K);
-static void mark_q8_cache(exec_state & st, const ggml_tensor * t, int kind) {
+static void mark_q8_cache(exec_state & st, const ggml_tensor * t, int kind = GGML_TYPE_Q8_K) {
     st.c->q8_src = t->data;
     st.c->q8_kind = kind;
     st.c->q8_bytes = ggml_abi_nbytes(t);
@@ -798,39 +854,22 @@ static void mark_q8_cache(exec_state & st, const ggml_tensor * t, int kind) {
 static bool can_defer_norm(const exec_state & st, int i, const ggml_tensor * n, const ggml_tensor * m, const ggml_tensor * x, const ggml_tensor * w) {
     if (ggml_abi_nrows(m) != 1 || (m->flags & GGML_TENSOR_FLAG_OUTPUT) || (n->flags & GGML_TENSOR_FLAG_OUTPUT)) return false;
     if (!ggml_abi_is_contiguous(x) || !ggml_abi_is_contiguous(m) || ((((uintptr_t) x->data) | ((uintptr_t) w->data) | ((uintptr_t) m->data)) & 15) || (x->ne[0] % 256) != 0 || x->ne[0] > 16384) return false;
-    const ggml_cgraph * g = st.g;
-    int last = -1, n_cons = 0;
-    for (int j = i + 2; j < g->n_nodes; ++j) {
-        const ggml_tensor * t = g->nodes[j];
-        for (int s = 0; s < GGML_MAX_SRC; ++s) {
-            if (t->src[s] != m) continue;
-            const ggml_tensor * wt = t->src[0];
-            const bool ok = t->op == GGML_OP_MUL_MAT && s == 1 && (is_kq23_type(wt->type) || is_iq4xs_type(wt->type) || wt->type == GGML_TYPE_Q4_K || wt->type == GGML_TYPE_Q5_K || wt->type == GGML_TYPE_Q6_K || wt->type == GGML_TYPE_Q8_0) &&
-                            wt->ne[2] == 1 && wt->ne[3] == 1 && ggml_abi_is_contiguous(t) && !(st.c->tp && buffer_is_rowpar(wt->view_src ? wt->view_src->buffer : wt->buffer)) &&
-                            !buffer_is_split(wt->buffer);  // (a split weight's devices are sent the f32 row: it has to be written)
-            if (!ok) return false;
-            last = j;
-            n_cons++;
-        }
-    }
-    if (n_cons == 0 || n_cons != use_count(st, m)) return false;
-    const char * x0 = (const char *) x->data;
-    const char * x1 = x0 + ggml_abi_nbytes(x);
+    // (every reader takes the mat-vec prologue: K = x->ne[0] is a multiple of 256 by the line above)
+    const int last = last_reader_if_all(st, i + 2, m, [&](const ggml_tensor * t, int s) {
+        const ggml_tensor * wt = t->src[0];
+        return t->op == GGML_OP_MUL_MAT && s == 1 && has_mmvq_prologue(wt->type, x->ne[0]) && wt->ne[2] == 1 && wt->ne[3] == 1 && ggml_abi_is_contiguous(t) &&
+               !(st.c->tp && weight_is_rowpar(wt)) && !buffer_is_split(wt->buffer);  // (a split weight's devices are sent the f32 row: it has to be written)
+    });
+    if (last < 0) return false;
+    // (ranges_overlap also says no for a node without data, which the plain range comparison here used to say as well: a range from address 0 ends below x)
     for (int j = i + 2; j <= last; ++j) {
-        const ggml_tensor * t = g->nodes[j];
-        if (t->op == GGML_OP_NONE || t->op == GGML_OP_VIEW || t->op == GGML_OP_RESHAPE || t->op == GGML_OP_PERMUTE || t->op == GGML_OP_TRANSPOSE) continue;
-        const char * t0 = (const char *) t->data;
-        const char * t1 = t0 + ggml_abi_nbytes(t);
-        if (t0 < x1 && x0 < t1) return false;
+        const ggml_tensor * t = st.g->nodes[j];
+        if (!is_view_op(t) && ranges_overlap(t, x)) return false;
     }
     return true;
 }
 
 // ------------------------------------------------------------------------------------------------ fused Q/K/V
-static bool ranges_overlap(const ggml_tensor * x, const ggml_tensor * y);
-static bool is_view_op(const ggml_tensor * t) {
-    return t->op == GGML_OP_NONE || t->op == GGML_OP_VIEW || t->op == GGML_OP_RESHAPE || t->op == GGML_OP_PERMUTE || t->op == GGML_OP_TRANSPOSE;
-}
 struct qkv_chain {
     const ggml_tensor * mm = nullptr;
     const ggml_tensor * bias = nullptr;
@@ -929,7 +968,7 @@ static bool try_fuse_qkv(exec_state & st, int i) {
         const ggml_tensor * t = g->nodes[k];
         if (t->op != GGML_OP_MUL_MAT || t->src[1] != X) continue;
         if (!kq(t->src[0]) || !ggml_abi_is_contiguous(t) || st.done[k]) return false;
-        if (c->tp && buffer_is_rowpar(t->src[0]->view_src ? t->src[0]->view_src->buffer : t->src[0]->buffer)) return false;
+        if (c->tp && weight_is_rowpar(t->src[0])) return false;
         qkv_chain ch;
         if (!follow_qkv_chain(st, k, limit, ch)) return false;
         chains.push_back(ch);
@@ -1010,16 +1049,7 @@ static bool try_fuse_qkv(exec_state & st, int i) {
             for (int k : ch.nodes)
                 if (ranges_overlap(g->nodes[k], dn->second.out)) base.norm_out = nullptr;
     if (rope0) {
-        rope_params p;
-        p.n_dims = rope0->op_params[1];
-        p.mode = rope0->op_params[2];
-        p.n_ctx_orig = rope0->op_params[4];
-        p.freq_base = ggml_abi_op_param_f32(rope0, 5);
-        p.freq_scale = ggml_abi_op_param_f32(rope0, 6);
-        p.ext_factor = ggml_abi_op_param_f32(rope0, 7);
-        p.attn_factor = ggml_abi_op_param_f32(rope0, 8);
-        p.beta_fast = ggml_abi_op_param_f32(rope0, 9);
-        p.beta_slow = ggml_abi_op_param_f32(rope0, 10);
+        const rope_params p = rope_params_of(rope0, false);
         rope_host_consts(p, base.theta_scale, base.corr0, base.corr1);
         base.head_dim = (int) rope0->ne[0];
         base.neox = (p.mode & GGML_ROPE_TYPE_NEOX) ? 1 : 0;
@@ -1028,7 +1058,6 @@ static bool try_fuse_qkv(exec_state & st, int i) {
         base.freq_scale = p.freq_scale;
         base.ext_factor = p.ext_factor;
         base.attn_factor = p.attn_factor;
-        memset(p.sections, 0, sizeof(p.sections));
         base.rope_tab = ensure_rope_table(st, base.pos, base.freq_factors, p, 1);
     } else {
         base.head_dim = 2;
@@ -1095,346 +1124,18 @@ static bool try_fuse_qkv(exec_state & st, int i) {
     return true;
 }
 
+// ------------------------------------------------------------------------------------------------ batches: rope + cache stores
+// At ROPE(q) of a batch: ROPE(k) with the same parameters and positions, SET_ROWS(k cache <- rope(k)) and SET_ROWS(v cache <- v)
+// with one index vector follow (llama.cpp's build_attn: q, k, v expanded together, then cpy_k / cpy_v) — four launches that
+// each sit at the launch floor for a few dozen tokens.  When only views (and the K / V projections already executed with the Q
+// projection: try_merge_mm_batch) sit between them, they run as one (ops.hip: k_rope_qk_store); absorbed nodes are flagged done.
+// (the window is recognised here, ahead of the sibling mat-muls, whose epilogues may take it over: try_merge_mm_batch)
 struct rope_store_plan {
     rope_store_args a{};
     int T = 0;
     int nodes[3] = {-1, -1, -1};                            // ROPE(k), SET_ROWS(k), SET_ROWS(v)
     const ggml_tensor * src[3] = {nullptr, nullptr, nullptr};  // what ROPE(q), ROPE(k) and SET_ROWS(v) read
 };
-static bool plan_rope_store(const exec_state & st, int i, rope_store_plan & pl);
-static const ggml_tensor * through_views(const ggml_tensor * t);
-
-// ------------------------------------------------------------------------------------------------ batches: sibling mat-muls
-// A batch's wq / wk / wv (and ffn_gate / ffn_up) multiply the same activations.  Launched one by one, the small ones cannot
-// fill the chip without a K split and its second kernel; as ONE launch over the concatenated row panels they can (mmq_i8.hip).
-// The siblings that follow node i in the graph are executed EARLY, at node i: legal when nothing between node i and a
-// sibling's own position reads or occupies the memory the sibling's result is written to (the graph allocator may have given
-// it a block that an earlier tensor still owns at node i's time).  Bias / residual ADDs directly after a member ride in its store.
-static bool ranges_overlap(const ggml_tensor * x, const ggml_tensor * y) {
-    if (!x->data || !y->data) return false;
-    const char * x0 = (const char *) x->data, * y0 = (const char *) y->data;
-    return x0 < y0 + ggml_abi_nbytes(y) && y0 < x0 + ggml_abi_nbytes(x);
-}
-static int try_merge_mm_batch(exec_state & st, int i) {  // returns the number of nodes consumed at position i (0: not merged)
-    backend_ctx * c = st.c;
-    ggml_cgraph * g = st.g;
-    ggml_tensor * n0 = g->nodes[i];
-    const ggml_tensor * X = n0->src[1];
-    const int type = n0->src[0]->type;
-    const int64_t K = n0->src[0]->ne[0], M = X->ne[1] * X->ne[2] * X->ne[3];
-    struct member { int k; ggml_tensor * dst; const ggml_tensor * add; int n_nodes; };
-    auto eligible = [&](const ggml_tensor * t, bool same_type = true) {
-        const ggml_tensor * w = t->src[0];
-        return t->op == GGML_OP_MUL_MAT && t->src[1] == X && (w->type == type) == same_type && w->ne[0] == K && w->ne[2] == 1 && w->ne[3] == 1 && rows_contig(w) &&
-               mmq_i8_supported(w->type, K, w->ne[1], M) && (w->ne[1] % 4) == 0 && t->type == GGML_TYPE_F32 && ggml_abi_is_contiguous(t) &&
-               !(tp_active(c) && buffer_is_rowpar(w->view_src ? w->view_src->buffer : w->buffer));
-    };
-    auto with_add = [&](int k) {  // member at node k, with the ADD that directly follows it folded in
-        ggml_tensor * t = g->nodes[k];
-        ggml_tensor * a1 = k + 1 < g->n_nodes ? g->nodes[k + 1] : nullptr;
-        const ggml_tensor * o1 = (a1 && !st.done[k + 1] && single_use(st, t)) ? add_partner(a1, t) : nullptr;
-        if (o1 && ggml_abi_is_contiguous(a1) && a1->type == GGML_TYPE_F32) {
-            // the sibling runs early, at node i: what it adds must exist by then (a bias is a weight; a residual produced
-            // between node i and the sibling's own position is not there yet)
-            bool ready = true;
-            for (int j = i; j <= k && ready; ++j) ready = !ranges_overlap(g->nodes[j], o1) || is_view_op(g->nodes[j]);
-            if (ready) return member{k, a1, o1, 2};
-        }
-        return member{k, t, nullptr, 1};
-    };
-    if (!eligible(n0)) return 0;
-    std::vector<member> ms{with_add(i)};
-    const int limit = std::min(g->n_nodes, i + 24);
-    std::vector<member> others;  // siblings stored in another format: not part of the launch, but pulled forward behind it (their
-                                 // projections then no longer sit between the ropes and the cache stores: try_fuse_rope_store)
-    for (int k = i + ms[0].n_nodes; k < limit && ms.size() + others.size() < 3; ++k) {
-        ggml_tensor * t = g->nodes[k];
-        if (st.done[k]) continue;
-        const bool same = eligible(t), other = !same && eligible(t, false);
-        if (!same && !other) continue;
-        const member m = with_add(k);
-        bool ok = true;
-        for (auto & o : ms) ok = ok && !ranges_overlap(m.dst, o.dst) && !ranges_overlap(m.dst, g->nodes[o.k]);
-        for (auto & o : others) ok = ok && !ranges_overlap(m.dst, o.dst) && !ranges_overlap(m.dst, g->nodes[o.k]);
-        for (int j = i + 1; j < k && ok; ++j) {  // everything that runs between node i and the sibling's own position
-            const ggml_tensor * u = g->nodes[j];
-            bool is_member = false;
-            for (auto & o : ms) is_member = is_member || j == o.k || (o.n_nodes == 2 && j == o.k + 1);
-            for (auto & o : others) is_member = is_member || j == o.k || (o.n_nodes == 2 && j == o.k + 1);
-            if (!is_view_op(u) && !is_member && ranges_overlap(m.dst, u)) ok = false;
-            for (int sidx = 0; sidx < GGML_MAX_SRC && ok; ++sidx)
-                if (u->src[sidx] && ranges_overlap(m.dst, u->src[sidx])) ok = false;
-        }
-        if (ok && m.add && ranges_overlap(m.dst, m.add) && m.add->data != m.dst->data) ok = false;
-        if (ok) (same ? ms : others).push_back(m);
-    }
-    // a decode step of a continuous batch: the sibling stored in another K-quant format (Q4_K_M keeps wv as Q6_K in half the layers) joins
-    // the launch — the skinny kernel serves two formats in two passes — instead of running alone on 32 workgroups behind it
-    bool mixed = false;
-    if (c->opt.mmq_skinny && c->opt.skinny_mix && M >= 2 && M <= 32 && ms.size() == 2 && others.size() == 1) {
-        int ty[3];
-        int64_t Ns[3], nb[3];
-        const member * all[3] = {&ms[0], &ms[1], &others[0]};
-        for (int q = 0; q < 3; ++q) {
-            const ggml_tensor * w = g->nodes[all[q]->k]->src[0];
-            ty[q] = w->type;
-            Ns[q] = w->ne[1];
-            nb[q] = (int64_t) w->nb[1];
-        }
-        if (mmq_skinny_mix_ok(ty, Ns, nb, 3, K, M)) {
-            ms.push_back(others[0]);
-            others.clear();
-            mixed = true;
-        }
-    }
-    if (ms.size() < 2) return 0;
-    int64_t n_total = 0;
-    mmq_mat_desc mats[3];
-    double wbytes = 0;
-    for (size_t q = 0; q < ms.size(); ++q) {
-        const ggml_tensor * w = g->nodes[ms[q].k]->src[0];
-        const ggml_tensor * add = ms[q].add;
-        const int64_t arows = add ? add->ne[1] * add->ne[2] * add->ne[3] : 0;
-        if ((ms[q].dst->nb[1] % 16) != 0) return 0;
-        mats[q] = {(const uint8_t *) w->data, (int64_t) w->nb[1], (int) w->ne[1], (float *) ms[q].dst->data, (int64_t) (ms[q].dst->nb[1] / 4),
-                   add ? (const float *) add->data : nullptr, (!add || arows == 1) ? 0 : (int64_t) (add->nb[1] / 4), (int) w->type == type ? 0 : (int) w->type};
-        n_total += w->ne[1];
-        wbytes += (double) ggml_abi_row_size(w->type, K) * (double) w->ne[1];
-    }
-    int ks = mmq_pick_ksplit(K, n_total, M, c->opt.mmq_skinny, type);
-    // -np decode steps: when these are the attention projections and ROPE(q), ROPE(k), SET_ROWS(k), SET_ROWS(v) follow (the window
-    // plan_rope_store recognises), the skinny launches rotate and store in their epilogue — no K split, no f32 projections, no rope launch
-    rope_store_plan epl;
-    int epi_node = -1;
-    mmq_epi epi{};
-    if (c->opt.fusion && c->opt.mmq_skinny && c->opt.skinny_rope && M <= 32 && st.rs_sk.node < 0) {
-        for (int k = i + ms[0].n_nodes; k < std::min(g->n_nodes, i + 24) && epi_node < 0; ++k)
-            if (!st.done[k] && !is_view_op(g->nodes[k])) {
-                bool member = false;
-                for (auto & o : ms) member = member || k == o.k || (o.n_nodes == 2 && k == o.k + 1);
-                for (auto & o : others) member = member || k == o.k || (o.n_nodes == 2 && k == o.k + 1);
-                if (!member) epi_node = k;
-            }
-        bool ok = epi_node >= 0 && g->nodes[epi_node]->op == GGML_OP_ROPE;
-        if (ok) {
-            // (the members behind node i are flagged done below; the plan's window walk must already see them that way)
-            std::vector<int> flagged;
-            for (size_t q = 1; q < ms.size(); ++q) for (int d = 0; d < ms[q].n_nodes; ++d) if (!st.done[ms[q].k + d]) { st.done[ms[q].k + d] = true; flagged.push_back(ms[q].k + d); }
-            for (auto & o : others) for (int d = 0; d < o.n_nodes; ++d) if (!st.done[o.k + d]) { st.done[o.k + d] = true; flagged.push_back(o.k + d); }
-            ok = plan_rope_store(st, epi_node, epl);
-            for (int f : flagged) st.done[f] = false;
-        }
-        // (all three in ONE launch only — a wv stored in another K-quant format has joined it above (skinny_mix).  A sibling left outside would run
-        // alone without its K split, 32 workgroups for 1024 rows, and cost more than the rope launch saves: measured 4.27 -> 4.40 ms per
-        // -np 32 step in round 2)
-        ok = ok && epl.a.p.mode == 0 && (epl.a.head_dim % 2) == 0 && ms.size() == 3 && others.empty();  // (V: cache rows, or — non-flash path — the elements of the transposed cache)
-        auto role_of = [&](const member & m) {
-            for (int sidx = 0; sidx < 3; ++sidx)
-                if (through_views(epl.src[sidx]) == m.dst) return sidx;
-            return -1;
-        };
-        auto member_ok = [&](const member & m, int64_t N) {
-            const int r = role_of(m);
-            const int64_t arows = m.add ? m.add->ne[1] * m.add->ne[2] * m.add->ne[3] : 0;
-            const ggml_tensor * w = g->nodes[m.k]->src[0];
-            return r >= 0 && use_count(st, m.dst) == 1 && !(m.dst->flags & GGML_TENSOR_FLAG_OUTPUT) && (!m.add || arows == 1) && (N % epl.a.head_dim) == 0 &&
-                   mmq_skinny_supported(w->type, K, N, M, (int64_t) w->nb[1]) &&
-                   N == (r == 0 ? (int64_t) epl.a.nh : (int64_t) epl.a.nkv) * epl.a.head_dim;
-        };
-        for (size_t q = 0; q < ms.size() && ok; ++q) ok = member_ok(ms[q], mats[q].N);
-        for (auto & o : others) ok = ok && member_ok(o, g->nodes[o.k]->src[0]->ne[1]);
-        // the rotation's (cos, sin) per (token, pair): the same for every layer of this graph run — computed once, by the first epilogue
-        if (ok) {
-            epi.tab = ensure_rope_table(st, epl.a.pos, epl.a.ff, epl.a.p, (int) M);
-            ok = epi.tab != nullptr;
-        }
-        if (ok) {
-            rope_host_consts(epl.a.p, epi.theta_scale, epi.corr0, epi.corr1);
-            epi.freq_scale = epl.a.p.freq_scale;
-            epi.ext_factor = epl.a.p.ext_factor;
-            epi.attn_factor = epl.a.p.attn_factor;
-            epi.pos = epl.a.pos;
-            epi.ff = epl.a.ff;
-            epi.idx = epl.a.idx;
-            epi.v_idx = epl.a.v_idx;
-            epi.head_dim = epl.a.head_dim;
-            epi.n_dims = epl.a.p.n_dims;
-            ks = 1;
-        } else
-            epi_node = -1;
-    }
-    auto epi_fill = [&](mmq_epi & e, int slot, int role) {  // role: 0 q, 1 k, 2 v
-        e.kind[slot] = role == 0 ? 1 : (role == 1 ? 2 : (epl.a.v_idx ? 4 : 3));
-        e.out[slot] = role == 0 ? epl.a.q_dst : (role == 1 ? epl.a.k_cache : epl.a.v_cache);
-        e.nb1[slot] = role == 0 ? epl.a.qd_nb1 : (role == 1 ? epl.a.kc_nb1 : epl.a.vc_nb1);
-        e.nb2[slot] = role == 0 ? epl.a.qd_nb2 : 0;
-    };
-    if ((size_t) ks * (size_t) M * (size_t) n_total * sizeof(float) > c->ws_size - st.aux_off && ks > 1) return 0;
-    const void * act = quantized_src1(st, X, type);
-    for (size_t q = 1; q < ms.size(); ++q)
-        for (int d = 0; d < ms[q].n_nodes; ++d) { mark_done(st, ms[q].k + d); c->st.fused_nodes++; }
-    for (auto & o : others)
-        for (int d = 0; d < o.n_nodes; ++d) mark_done(st, o.k + d);
-    // K split and the results are read only by the rope + cache-store kernel that follows (attention projections of a small batch):
-    // that kernel sums the partial products itself — no reduce pass, and the f32 projections are never written
-    bool defer = false;
-    int jr = -1;
-    if (ks > 1 && c->opt.fusion && st.rs_sk.node < 0 && epi_node < 0) {
-        for (int k = i + ms[0].n_nodes; k < std::min(g->n_nodes, i + 24) && jr < 0; ++k)
-            if (!st.done[k] && !is_view_op(g->nodes[k])) jr = k;
-        rope_store_plan pl;
-        if (jr >= 0 && plan_rope_store(st, jr, pl)) {
-            defer = true;
-            for (size_t q = 0; q < ms.size() && defer; ++q) {
-                bool mapped = false;
-                for (int sidx = 0; sidx < 3; ++sidx) mapped = mapped || through_views(pl.src[sidx]) == ms[q].dst;
-                const int64_t arows = ms[q].add ? ms[q].add->ne[1] * ms[q].add->ne[2] * ms[q].add->ne[3] : 0;
-                // every reader of the projection must be that kernel (one reshape in between), and a folded ADD must be a bias row
-                defer = mapped && use_count(st, ms[q].dst) == 1 && !(ms[q].dst->flags & GGML_TENSOR_FLAG_OUTPUT) && (!ms[q].add || arows == 1) &&
-                        (mats[q].N % pl.a.head_dim) == 0;
-            }
-        }
-    }
-    float * part = (float *) ((char *) c->ws + st.aux_off);
-    {
-        timed_scope ts(c, (std::string("mmq_") + type_tag(type) + (mixed ? std::string("+") + type_tag(g->nodes[ms.back().k]->src[0]->type) : std::string()) + (ms.size() == 3 ? "_x3" : "_x2") + "_n" +
-                           std::to_string(n_total) + "_k" + std::to_string(K)).c_str(), wbytes, true);
-        if (epi_node >= 0) {
-            auto role_of2 = [&](const member & m) {
-                for (int sidx = 0; sidx < 3; ++sidx)
-                    if (through_views(epl.src[sidx]) == m.dst) return sidx;
-                return -1;
-            };
-            for (size_t q = 0; q < ms.size(); ++q) epi_fill(epi, (int) q, role_of2(ms[q]));
-        }
-        const int served = launch_mmq_i8_multi(c->stream, type, (int) ms.size(), mats, (int) K, (int) M, act, c->opt.mmq_bn, ks, part, !defer, c->opt.mmq_skinny, epi_node >= 0 ? &epi : nullptr);
-        c->st.skinny_launches += served == 1;
-        c->st.wide_launches += served == 2;
-            c->st.tiled_launches += served == 0;
-    }
-    c->st.kernel_launches += (ks > 1 && !defer) ? 2 : 1;
-    c->st.fused_nodes += ms[0].n_nodes - 1;
-    size_t aux_bump = 0;
-    if (defer) {
-        st.rs_sk.node = jr;
-        st.rs_sk.n = (int) ms.size();
-        st.rs_sk.ks = ks;
-        st.rs_sk.M = (int) M;
-        st.rs_sk.part = part;
-        for (size_t q = 0; q < ms.size(); ++q) { st.rs_sk.mats[q] = mats[q]; st.rs_sk.dst[q] = ms[q].dst; }
-        aux_bump = ((size_t) ks * (size_t) M * (size_t) n_total * sizeof(float) + 255) & ~(size_t) 255;  // the partials stay live: later launches use the space behind them
-    }
-    st.aux_off += aux_bump;
-    for (auto & o : others) {
-        if (epi_node >= 0) {
-            int role = -1;
-            for (int sidx = 0; sidx < 3; ++sidx)
-                if (through_views(epl.src[sidx]) == o.dst) role = sidx;
-            st.epi = epi;
-            for (int q = 0; q < 3; ++q) st.epi.kind[q] = 0;
-            epi_fill(st.epi, 0, role);
-            st.epi_dst = o.dst;
-        }
-        const bool ok_o = run_mul_mat_q(st, g->nodes[o.k]->src[0], nullptr, X, o.dst, o.add, nullptr);
-        st.epi_dst = nullptr;
-        if (!ok_o) { st.aux_off -= aux_bump; return -1; }
-        c->st.fused_nodes += o.n_nodes - 1;
-    }
-    st.aux_off -= aux_bump;
-    if (epi_node >= 0) {  // ROPE(q), ROPE(k), SET_ROWS(k), SET_ROWS(v) happened in the epilogues
-        mark_done(st, epi_node);
-        for (int k : epl.nodes) mark_done(st, k);
-        c->st.fused_nodes += 4;
-        c->st.rope_epilogues++;
-    }
-    return ms[0].n_nodes;
-}
-
-// Q8_0 weights, 9 .. 128 columns (round 6): wq / wk / wv (and gate / up) of a batch multiply the same activations — one launch of the weight-streaming matrix-core
-// kernel over the concatenated 32-row panels (mmq_q80.hip), bias ADDs folded into the store.  The member search is try_merge_mm_batch's (same dependence rules);
-// no K split, no epilogues: with the K / V projections out of the way the ropes and cache stores that follow fuse as they do for the K-quants (try_fuse_rope_store).
-static int try_merge_q80_skinny(exec_state & st, int i) {  // returns the number of nodes consumed at position i (0: not merged)
-    backend_ctx * c = st.c;
-    ggml_cgraph * g = st.g;
-    ggml_tensor * n0 = g->nodes[i];
-    const ggml_tensor * X = n0->src[1];
-    const int64_t K = n0->src[0]->ne[0], M = X->ne[1] * X->ne[2] * X->ne[3];
-    struct member { int k; ggml_tensor * dst; const ggml_tensor * add; int n_nodes; };
-    auto eligible = [&](const ggml_tensor * t) {
-        const ggml_tensor * w = t->src[0];
-        return t->op == GGML_OP_MUL_MAT && t->src[1] == X && w->type == GGML_TYPE_Q8_0 && w->ne[0] == K && w->ne[2] == 1 && w->ne[3] == 1 && rows_contig(w) && !buffer_is_split(w->buffer) &&
-               mmq_q80_skinny_supported(w->type, K, w->ne[1], M) && t->type == GGML_TYPE_F32 && ggml_abi_is_contiguous(t) && !(tp_active(c) && buffer_is_rowpar(w->view_src ? w->view_src->buffer : w->buffer));
-    };
-    auto with_add = [&](int k) {  // member at node k, with the ADD that directly follows it folded in
-        ggml_tensor * t = g->nodes[k];
-        ggml_tensor * a1 = k + 1 < g->n_nodes ? g->nodes[k + 1] : nullptr;
-        const ggml_tensor * o1 = (a1 && !st.done[k + 1] && single_use(st, t)) ? add_partner(a1, t) : nullptr;
-        if (o1 && ggml_abi_is_contiguous(a1) && a1->type == GGML_TYPE_F32) {
-            bool ready = true;  // (the sibling runs early, at node i: what it adds must exist by then)
-            for (int j = i; j <= k && ready; ++j) ready = !ranges_overlap(g->nodes[j], o1) || is_view_op(g->nodes[j]);
-            if (ready) return member{k, a1, o1, 2};
-        }
-        return member{k, t, nullptr, 1};
-    };
-    if (!eligible(n0)) return 0;
-    std::vector<member> ms{with_add(i)};
-    const int limit = std::min(g->n_nodes, i + 24);
-    for (int k = i + ms[0].n_nodes; k < limit && ms.size() < 3; ++k) {
-        ggml_tensor * t = g->nodes[k];
-        if (st.done[k] || !eligible(t)) continue;
-        const member m = with_add(k);
-        bool ok = true;
-        for (auto & o : ms) ok = ok && !ranges_overlap(m.dst, o.dst) && !ranges_overlap(m.dst, g->nodes[o.k]);
-        for (int j = i + 1; j < k && ok; ++j) {  // everything that runs between node i and the sibling's own position
-            const ggml_tensor * u = g->nodes[j];
-            bool is_member = false;
-            for (auto & o : ms) is_member = is_member || j == o.k || (o.n_nodes == 2 && j == o.k + 1);
-            if (!is_view_op(u) && !is_member && ranges_overlap(m.dst, u)) ok = false;
-            for (int sidx = 0; sidx < GGML_MAX_SRC && ok; ++sidx)
-                if (u->src[sidx] && ranges_overlap(m.dst, u->src[sidx])) ok = false;
-        }
-        if (ok && m.add && ranges_overlap(m.dst, m.add) && m.add->data != m.dst->data) ok = false;
-        if (ok) ms.push_back(m);
-    }
-    if (ms.size() < 2) return 0;
-    mmq80s_desc mats[3];
-    double wbytes = 0;
-    int64_t n_total = 0;
-    int with_copy = 0;
-    for (size_t q = 0; q < ms.size(); ++q) {
-        const ggml_tensor * w = g->nodes[ms[q].k]->src[0];
-        const ggml_tensor * add = ms[q].add;
-        const int64_t arows = add ? add->ne[1] * add->ne[2] * add->ne[3] : 0;
-        mats[q] = {(const uint8_t *) w->data, q80_panel_copy(c, w), (int64_t) w->nb[1], (int) w->ne[1], (float *) ms[q].dst->data, (int64_t) (ms[q].dst->nb[1] / 4),
-                   add ? (const float *) add->data : nullptr, (!add || arows == 1) ? 0 : (int64_t) (add->nb[1] / 4)};
-        with_copy += mats[q].W_panels != nullptr;
-        n_total += w->ne[1];
-        wbytes += (double) ggml_abi_row_size(w->type, K) * (double) w->ne[1];
-    }
-    if (with_copy != 0 && with_copy != (int) ms.size()) return 0;  // (one template form per launch: all from their panel copies, or none)
-    const void * act = quantized_src1(st, X, MI_ACT_Q80_PANEL);
-    for (size_t q = 1; q < ms.size(); ++q)
-        for (int d = 0; d < ms[q].n_nodes; ++d) { mark_done(st, ms[q].k + d); c->st.fused_nodes++; }
-    {
-        timed_scope ts(c, (std::string("mmq_q8_0_skinny") + (ms.size() == 3 ? "_x3" : "_x2") + "_n" + std::to_string(n_total) + "_k" + std::to_string(K)).c_str(), wbytes, true);
-        launch_mmq_q80_skinny_multi(c->stream, (int) ms.size(), mats, (int) K, (int) M, act);
-    }
-    c->st.decode_copy_launches += with_copy != 0;
-    c->st.skinny_launches++;
-    c->st.kernel_launches++;
-    c->st.fused_nodes += ms[0].n_nodes - 1;
-    return ms[0].n_nodes;
-}
-
-// ------------------------------------------------------------------------------------------------ batches: rope + cache stores
-// At ROPE(q) of a batch: ROPE(k) with the same parameters and positions, SET_ROWS(k cache <- rope(k)) and SET_ROWS(v cache <- v)
-// with one index vector follow (llama.cpp's build_attn: q, k, v expanded together, then cpy_k / cpy_v) — four launches that
-// each sit at the launch floor for a few dozen tokens.  When only views (and the K / V projections already executed with the Q
-// projection: try_merge_mm_batch) sit between them, they run as one (ops.hip: k_rope_qk_store); absorbed nodes are flagged done.
-static const ggml_tensor * through_views(const ggml_tensor * t) {
-    while (t && (t->op == GGML_OP_RESHAPE || t->op == GGML_OP_VIEW) && t->src[0] && t->data == t->src[0]->data) t = t->src[0];
-    return t;
-}
 static bool plan_rope_store(const exec_state & st, int i, rope_store_plan & pl) {
     ggml_cgraph * g = st.g;
     const ggml_tensor * rq = g->nodes[i];
@@ -1489,16 +1190,7 @@ static bool plan_rope_store(const exec_state & st, int i, rope_store_plan & pl) 
     a.v_idx = v_scatter ? (const int64_t *) vs->src[1]->data : nullptr;
     a.pos = (const int32_t *) rq->src[1]->data;
     a.ff = rq->src[2] ? (const float *) rq->src[2]->data : nullptr;
-    a.p.n_dims = rq->op_params[1];
-    a.p.mode = rq->op_params[2];
-    a.p.n_ctx_orig = rq->op_params[4];
-    a.p.freq_base = ggml_abi_op_param_f32(rq, 5);
-    a.p.freq_scale = ggml_abi_op_param_f32(rq, 6);
-    a.p.ext_factor = ggml_abi_op_param_f32(rq, 7);
-    a.p.attn_factor = ggml_abi_op_param_f32(rq, 8);
-    a.p.beta_fast = ggml_abi_op_param_f32(rq, 9);
-    a.p.beta_slow = ggml_abi_op_param_f32(rq, 10);
-    memset(a.p.sections, 0, sizeof(a.p.sections));
+    a.p = rope_params_of(rq, false);
     a.nh = (int) NH; a.nkv = (int) NKV; a.head_dim = (int) HD;
     pl.a = a;
     pl.T = (int) T;
@@ -1506,7 +1198,13 @@ static bool plan_rope_store(const exec_state & st, int i, rope_store_plan & pl) 
     pl.src[0] = q; pl.src[1] = ksrc; pl.src[2] = vsrc;
     return true;
 }
-static void flush_deferred_qkv(exec_state & st);
+// the reader the unsummed projections were left for did not materialise: run their reduce pass now
+static void flush_deferred_qkv(exec_state & st) {
+    if (st.rs_sk.node < 0) return;
+    launch_splitk_reduce_mats(st.c->stream, st.rs_sk.n, st.rs_sk.mats, st.rs_sk.part, st.rs_sk.ks, st.rs_sk.M);
+    st.c->st.kernel_launches++;
+    st.rs_sk.node = -1;
+}
 static bool try_fuse_rope_store(exec_state & st, int i) {
     backend_ctx * c = st.c;
     rope_store_plan pl;
@@ -1538,12 +1236,294 @@ static bool try_fuse_rope_store(exec_state & st, int i) {
     for (int k : pl.nodes) { mark_done(st, k); c->st.fused_nodes++; }
     return true;
 }
-// the reader the unsummed projections were left for did not materialise: run their reduce pass now
-static void flush_deferred_qkv(exec_state & st) {
-    if (st.rs_sk.node < 0) return;
-    launch_splitk_reduce_mats(st.c->stream, st.rs_sk.n, st.rs_sk.mats, st.rs_sk.part, st.rs_sk.ks, st.rs_sk.M);
-    st.c->st.kernel_launches++;
-    st.rs_sk.node = -1;
+
+// ------------------------------------------------------------------------------------------------ batches: sibling mat-muls
+// A batch's wq / wk / wv (and ffn_gate / ffn_up) multiply the same activations.  Launched one by one, the small ones cannot
+// fill the chip without a K split and its second kernel; as ONE launch over the concatenated row panels they can (mmq_i8.hip).
+// The siblings that follow node i in the graph are executed EARLY, at node i: legal when nothing between node i and a
+// sibling's own position reads or occupies the memory the sibling's result is written to (the graph allocator may have given
+// it a block that an earlier tensor still owns at node i's time).  Bias / residual ADDs directly after a member ride in its store.
+struct mm_member { int k; ggml_tensor * dst; const ggml_tensor * add; int n_nodes; };  // the mat-mul at node k, with the ADD that directly follows it folded in (n_nodes 2: dst is the ADD)
+enum sibling_role { SIB_NO, SIB_JOINS, SIB_PULLED };
+struct mm_siblings {
+    std::vector<mm_member> ms;      // node i and the siblings that join its launch
+    std::vector<mm_member> others;  // siblings not part of the launch, but pulled forward behind it
+    bool holds(int j) const {       // is node j part of a member
+        for (const std::vector<mm_member> * v : {&ms, &others})
+            for (const mm_member & o : *v)
+                if (j == o.k || (o.n_nodes == 2 && j == o.k + 1)) return true;
+        return false;
+    }
+};
+// The member search of both merges: node i (which must itself join) and up to two more among the next 24 nodes, each asked of role(t).  false: node i does not qualify.
+template <class Role>
+static bool find_mm_siblings(const exec_state & st, int i, Role && role, mm_siblings & sb) {
+    const ggml_cgraph * g = st.g;
+    auto with_add = [&](int k) {
+        ggml_tensor * t = g->nodes[k];
+        ggml_tensor * a1 = k + 1 < g->n_nodes ? g->nodes[k + 1] : nullptr;
+        const ggml_tensor * o1 = (a1 && !st.done[k + 1] && single_use(st, t)) ? add_partner(a1, t) : nullptr;
+        if (o1 && ggml_abi_is_contiguous(a1) && a1->type == GGML_TYPE_F32) {
+            // the sibling runs early, at node i: what it adds must exist by then (a bias is a weight; a residual produced
+            // between node i and the sibling's own position is not there yet)
+            bool ready = true;
+            for (int j = i; j <= k && ready; ++j) ready = !ranges_overlap(g->nodes[j], o1) || is_view_op(g->nodes[j]);
+            if (ready) return mm_member{k, a1, o1, 2};
+        }
+        return mm_member{k, t, nullptr, 1};
+    };
+    if (role(g->nodes[i]) != SIB_JOINS) return false;
+    sb.ms.push_back(with_add(i));
+    const int limit = std::min(g->n_nodes, i + 24);
+    for (int k = i + sb.ms[0].n_nodes; k < limit && sb.ms.size() + sb.others.size() < 3; ++k) {
+        if (st.done[k]) continue;
+        const sibling_role r = role(g->nodes[k]);
+        if (r == SIB_NO) continue;
+        const mm_member m = with_add(k);
+        bool ok = true;
+        for (const std::vector<mm_member> * v : {&sb.ms, &sb.others})
+            for (const mm_member & o : *v) ok = ok && !ranges_overlap(m.dst, o.dst) && !ranges_overlap(m.dst, g->nodes[o.k]);
+        for (int j = i + 1; j < k && ok; ++j) {  // everything that runs between node i and the sibling's own position
+            const ggml_tensor * u = g->nodes[j];
+            if (!is_view_op(u) && !sb.holds(j) && ranges_overlap(m.dst, u)) ok = false;
+            for (int sidx = 0; sidx < GGML_MAX_SRC && ok; ++sidx)
+                if (u->src[sidx] && ranges_overlap(m.dst, u->src[sidx])) ok = false;
+        }
+        if (ok && m.add && ranges_overlap(m.dst, m.add) && m.add->data != m.dst->data) ok = false;
+        if (ok) (r == SIB_JOINS ? sb.ms : sb.others).push_back(m);
+    }
+    return true;
+}
+static int try_merge_mm_batch(exec_state & st, int i) {  // returns the number of nodes consumed at position i (0: not merged)
+    backend_ctx * c = st.c;
+    ggml_cgraph * g = st.g;
+    ggml_tensor * n0 = g->nodes[i];
+    const ggml_tensor * X = n0->src[1];
+    const int type = n0->src[0]->type;
+    const int64_t K = n0->src[0]->ne[0], M = X->ne[1] * X->ne[2] * X->ne[3];
+    mm_siblings sb;
+    // siblings stored in another format are not part of the launch, but pulled forward behind it (their projections then no longer sit between the ropes and the
+    // cache stores: try_fuse_rope_store)
+    if (!find_mm_siblings(st, i, [&](const ggml_tensor * t) {
+            const ggml_tensor * w = t->src[0];
+            const bool ok = t->op == GGML_OP_MUL_MAT && t->src[1] == X && w->ne[0] == K && w->ne[2] == 1 && w->ne[3] == 1 && rows_contig(w) &&
+                            mmq_i8_supported(w->type, K, w->ne[1], M) && (w->ne[1] % 4) == 0 && t->type == GGML_TYPE_F32 && ggml_abi_is_contiguous(t) &&
+                            !(tp_active(c) && weight_is_rowpar(w));
+            return !ok ? SIB_NO : (w->type == type ? SIB_JOINS : SIB_PULLED);
+        }, sb))
+        return 0;
+    std::vector<mm_member> & ms = sb.ms, & others = sb.others;
+    // a decode step of a continuous batch: the sibling stored in another K-quant format (Q4_K_M keeps wv as Q6_K in half the layers) joins
+    // the launch — the skinny kernel serves two formats in two passes — instead of running alone on 32 workgroups behind it
+    bool mixed = false;
+    if (c->opt.mmq_skinny && c->opt.skinny_mix && M >= 2 && M <= 32 && ms.size() == 2 && others.size() == 1) {
+        int ty[3];
+        int64_t Ns[3], nb[3];
+        const mm_member * all[3] = {&ms[0], &ms[1], &others[0]};
+        for (int q = 0; q < 3; ++q) {
+            const ggml_tensor * w = g->nodes[all[q]->k]->src[0];
+            ty[q] = w->type;
+            Ns[q] = w->ne[1];
+            nb[q] = (int64_t) w->nb[1];
+        }
+        if (mmq_skinny_mix_ok(ty, Ns, nb, 3, K, M)) {
+            ms.push_back(others[0]);
+            others.clear();
+            mixed = true;
+        }
+    }
+    if (ms.size() < 2) return 0;
+    int64_t n_total = 0;
+    mmq_mat_desc mats[3];
+    double wbytes = 0;
+    for (size_t q = 0; q < ms.size(); ++q) {
+        const ggml_tensor * w = g->nodes[ms[q].k]->src[0];
+        const ggml_tensor * add = ms[q].add;
+        if ((ms[q].dst->nb[1] % 16) != 0) return 0;
+        mats[q] = {(const uint8_t *) w->data, (int64_t) w->nb[1], (int) w->ne[1], (float *) ms[q].dst->data, (int64_t) (ms[q].dst->nb[1] / 4),
+                   add ? (const float *) add->data : nullptr, addend_stride(add), (int) w->type == type ? 0 : (int) w->type};
+        n_total += w->ne[1];
+        wbytes += (double) ggml_abi_row_size(w->type, K) * (double) w->ne[1];
+    }
+    int ks = mmq_pick_ksplit(K, n_total, M, c->opt.mmq_skinny, type);
+    // -np decode steps: when these are the attention projections and ROPE(q), ROPE(k), SET_ROWS(k), SET_ROWS(v) follow (the window
+    // plan_rope_store recognises), the skinny launches rotate and store in their epilogue — no K split, no f32 projections, no rope launch
+    rope_store_plan epl;
+    int epi_node = -1;
+    mmq_epi epi{};
+    // which of the plan's sources the member produces: 0 q, 1 k, 2 v.  (The first match; the copy of this search for a pulled sibling used to keep the last.  The
+    // plan's three sources are distinct tensors, so at most one matches — and that site runs only with epi_node >= 0, which asks for others.empty())
+    auto role_of = [&](const mm_member & m) {
+        for (int sidx = 0; sidx < 3; ++sidx)
+            if (through_views(epl.src[sidx]) == m.dst) return sidx;
+        return -1;
+    };
+    if (c->opt.fusion && c->opt.mmq_skinny && c->opt.skinny_rope && M <= 32 && st.rs_sk.node < 0) {
+        for (int k = i + ms[0].n_nodes; k < std::min(g->n_nodes, i + 24) && epi_node < 0; ++k)
+            if (!st.done[k] && !is_view_op(g->nodes[k]) && !sb.holds(k)) epi_node = k;
+        bool ok = epi_node >= 0 && g->nodes[epi_node]->op == GGML_OP_ROPE;
+        if (ok) {
+            // (the members behind node i are flagged done below; the plan's window walk must already see them that way)
+            std::vector<int> flagged;
+            for (size_t q = 1; q < ms.size(); ++q) for (int d = 0; d < ms[q].n_nodes; ++d) if (!st.done[ms[q].k + d]) { st.done[ms[q].k + d] = true; flagged.push_back(ms[q].k + d); }
+            for (auto & o : others) for (int d = 0; d < o.n_nodes; ++d) if (!st.done[o.k + d]) { st.done[o.k + d] = true; flagged.push_back(o.k + d); }
+            ok = plan_rope_store(st, epi_node, epl);
+            for (int f : flagged) st.done[f] = false;
+        }
+        // (all three in ONE launch only — a wv stored in another K-quant format has joined it above (skinny_mix).  A sibling left outside would run
+        // alone without its K split, 32 workgroups for 1024 rows, and cost more than the rope launch saves: measured 4.27 -> 4.40 ms per
+        // -np 32 step in round 2)
+        ok = ok && epl.a.p.mode == 0 && (epl.a.head_dim % 2) == 0 && ms.size() == 3 && others.empty();  // (V: cache rows, or — non-flash path — the elements of the transposed cache)
+        auto member_ok = [&](const mm_member & m, int64_t N) {
+            const int r = role_of(m);
+            const ggml_tensor * w = g->nodes[m.k]->src[0];
+            return r >= 0 && use_count(st, m.dst) == 1 && !(m.dst->flags & GGML_TENSOR_FLAG_OUTPUT) && (!m.add || ggml_abi_nrows(m.add) == 1) && (N % epl.a.head_dim) == 0 &&
+                   mmq_skinny_supported(w->type, K, N, M, (int64_t) w->nb[1]) &&
+                   N == (r == 0 ? (int64_t) epl.a.nh : (int64_t) epl.a.nkv) * epl.a.head_dim;
+        };
+        for (size_t q = 0; q < ms.size() && ok; ++q) ok = member_ok(ms[q], mats[q].N);
+        for (auto & o : others) ok = ok && member_ok(o, g->nodes[o.k]->src[0]->ne[1]);
+        // the rotation's (cos, sin) per (token, pair): the same for every layer of this graph run — computed once, by the first epilogue
+        if (ok) {
+            epi.tab = ensure_rope_table(st, epl.a.pos, epl.a.ff, epl.a.p, (int) M);
+            ok = epi.tab != nullptr;
+        }
+        if (ok) {
+            rope_host_consts(epl.a.p, epi.theta_scale, epi.corr0, epi.corr1);
+            epi.freq_scale = epl.a.p.freq_scale;
+            epi.ext_factor = epl.a.p.ext_factor;
+            epi.attn_factor = epl.a.p.attn_factor;
+            epi.pos = epl.a.pos;
+            epi.ff = epl.a.ff;
+            epi.idx = epl.a.idx;
+            epi.v_idx = epl.a.v_idx;
+            epi.head_dim = epl.a.head_dim;
+            epi.n_dims = epl.a.p.n_dims;
+            ks = 1;
+        } else
+            epi_node = -1;
+    }
+    auto epi_fill = [&](mmq_epi & e, int slot, int role) {  // role: 0 q, 1 k, 2 v
+        e.kind[slot] = role == 0 ? 1 : (role == 1 ? 2 : (epl.a.v_idx ? 4 : 3));
+        e.out[slot] = role == 0 ? epl.a.q_dst : (role == 1 ? epl.a.k_cache : epl.a.v_cache);
+        e.nb1[slot] = role == 0 ? epl.a.qd_nb1 : (role == 1 ? epl.a.kc_nb1 : epl.a.vc_nb1);
+        e.nb2[slot] = role == 0 ? epl.a.qd_nb2 : 0;
+    };
+    if ((size_t) ks * (size_t) M * (size_t) n_total * sizeof(float) > c->ws_size - st.aux_off && ks > 1) return 0;
+    const void * act = quantized_src1(st, X, type);
+    for (size_t q = 1; q < ms.size(); ++q)
+        for (int d = 0; d < ms[q].n_nodes; ++d) { mark_done(st, ms[q].k + d); c->st.fused_nodes++; }
+    for (auto & o : others)
+        for (int d = 0; d < o.n_nodes; ++d) mark_done(st, o.k + d);
+    // K split and the results are read only by the rope + cache-store kernel that follows (attention projections of a small batch):
+    // that kernel sums the partial products itself — no reduce pass, and the f32 projections are never written
+    bool defer = false;
+    int jr = -1;
+    if (ks > 1 && c->opt.fusion && st.rs_sk.node < 0 && epi_node < 0) {
+        for (int k = i + ms[0].n_nodes; k < std::min(g->n_nodes, i + 24) && jr < 0; ++k)
+            if (!st.done[k] && !is_view_op(g->nodes[k])) jr = k;
+        rope_store_plan pl;
+        if (jr >= 0 && plan_rope_store(st, jr, pl)) {
+            defer = true;
+            for (size_t q = 0; q < ms.size() && defer; ++q) {
+                bool mapped = false;
+                for (int sidx = 0; sidx < 3; ++sidx) mapped = mapped || through_views(pl.src[sidx]) == ms[q].dst;
+                // every reader of the projection must be that kernel (one reshape in between), and a folded ADD must be a bias row
+                defer = mapped && use_count(st, ms[q].dst) == 1 && !(ms[q].dst->flags & GGML_TENSOR_FLAG_OUTPUT) && (!ms[q].add || ggml_abi_nrows(ms[q].add) == 1) &&
+                        (mats[q].N % pl.a.head_dim) == 0;
+            }
+        }
+    }
+    float * part = (float *) ((char *) c->ws + st.aux_off);
+    {
+        timed_scope ts(c, (std::string("mmq_") + type_tag(type) + (mixed ? std::string("+") + type_tag(g->nodes[ms.back().k]->src[0]->type) : std::string()) + (ms.size() == 3 ? "_x3" : "_x2") + "_n" +
+                           std::to_string(n_total) + "_k" + std::to_string(K)).c_str(), wbytes, true);
+        if (epi_node >= 0)
+            for (size_t q = 0; q < ms.size(); ++q) epi_fill(epi, (int) q, role_of(ms[q]));
+        const int served = launch_mmq_i8_multi(c->stream, type, (int) ms.size(), mats, (int) K, (int) M, act, c->opt.mmq_bn, ks, part, !defer, c->opt.mmq_skinny, epi_node >= 0 ? &epi : nullptr);
+        c->st.skinny_launches += served == 1;
+        c->st.wide_launches += served == 2;
+        c->st.tiled_launches += served == 0;
+    }
+    c->st.kernel_launches += (ks > 1 && !defer) ? 2 : 1;
+    c->st.fused_nodes += ms[0].n_nodes - 1;
+    size_t aux_bump = 0;
+    if (defer) {
+        st.rs_sk.node = jr;
+        st.rs_sk.n = (int) ms.size();
+        st.rs_sk.ks = ks;
+        st.rs_sk.M = (int) M;
+        st.rs_sk.part = part;
+        for (size_t q = 0; q < ms.size(); ++q) { st.rs_sk.mats[q] = mats[q]; st.rs_sk.dst[q] = ms[q].dst; }
+        aux_bump = ((size_t) ks * (size_t) M * (size_t) n_total * sizeof(float) + 255) & ~(size_t) 255;  // the partials stay live: later launches use the space behind them
+    }
+    st.aux_off += aux_bump;
+    for (auto & o : others) {
+        if (epi_node >= 0) {
+            st.epi = epi;
+            for (int q = 0; q < 3; ++q) st.epi.kind[q] = 0;
+            epi_fill(st.epi, 0, role_of(o));
+            st.epi_dst = o.dst;
+        }
+        const bool ok_o = run_mul_mat_q(st, g->nodes[o.k]->src[0], nullptr, X, o.dst, o.add, nullptr);
+        st.epi_dst = nullptr;
+        if (!ok_o) { st.aux_off -= aux_bump; return -1; }
+        c->st.fused_nodes += o.n_nodes - 1;
+    }
+    st.aux_off -= aux_bump;
+    if (epi_node >= 0) {  // ROPE(q), ROPE(k), SET_ROWS(k), SET_ROWS(v) happened in the epilogues
+        mark_done(st, epi_node);
+        for (int k : epl.nodes) mark_done(st, k);
+        c->st.fused_nodes += 4;
+        c->st.rope_epilogues++;
+    }
+    return ms[0].n_nodes;
+}
+
+// Q8_0 weights, 9 .. 128 columns (round 6): wq / wk / wv (and gate / up) of a batch multiply the same activations — one launch of the weight-streaming matrix-core
+// kernel over the concatenated 32-row panels (mmq_q80.hip), bias ADDs folded into the store.  Same member search, same dependence rules (find_mm_siblings);
+// no K split, no epilogues: with the K / V projections out of the way the ropes and cache stores that follow fuse as they do for the K-quants (try_fuse_rope_store).
+static int try_merge_q80_skinny(exec_state & st, int i) {  // returns the number of nodes consumed at position i (0: not merged)
+    backend_ctx * c = st.c;
+    ggml_cgraph * g = st.g;
+    const ggml_tensor * X = g->nodes[i]->src[1];
+    const int64_t K = g->nodes[i]->src[0]->ne[0], M = X->ne[1] * X->ne[2] * X->ne[3];
+    mm_siblings sb;
+    if (!find_mm_siblings(st, i, [&](const ggml_tensor * t) {
+            const ggml_tensor * w = t->src[0];
+            const bool ok = t->op == GGML_OP_MUL_MAT && t->src[1] == X && w->type == GGML_TYPE_Q8_0 && w->ne[0] == K && w->ne[2] == 1 && w->ne[3] == 1 && rows_contig(w) && !buffer_is_split(w->buffer) &&
+                            mmq_q80_skinny_supported(w->type, K, w->ne[1], M) && t->type == GGML_TYPE_F32 && ggml_abi_is_contiguous(t) && !(tp_active(c) && weight_is_rowpar(w));
+            return ok ? SIB_JOINS : SIB_NO;
+        }, sb))
+        return 0;
+    const std::vector<mm_member> & ms = sb.ms;
+    if (ms.size() < 2) return 0;
+    mmq80s_desc mats[3];
+    double wbytes = 0;
+    int64_t n_total = 0;
+    int with_copy = 0;
+    for (size_t q = 0; q < ms.size(); ++q) {
+        const ggml_tensor * w = g->nodes[ms[q].k]->src[0];
+        const ggml_tensor * add = ms[q].add;
+        mats[q] = {(const uint8_t *) w->data, q80_panel_copy(c, w), (int64_t) w->nb[1], (int) w->ne[1], (float *) ms[q].dst->data, (int64_t) (ms[q].dst->nb[1] / 4),
+                   add ? (const float *) add->data : nullptr, addend_stride(add)};
+        with_copy += mats[q].W_panels != nullptr;
+        n_total += w->ne[1];
+        wbytes += (double) ggml_abi_row_size(w->type, K) * (double) w->ne[1];
+    }
+    if (with_copy != 0 && with_copy != (int) ms.size()) return 0;  // (one template form per launch: all from their panel copies, or none)
+    const void * act = quantized_src1(st, X, MI_ACT_Q80_PANEL);
+    for (size_t q = 1; q < ms.size(); ++q)
+        for (int d = 0; d < ms[q].n_nodes; ++d) { mark_done(st, ms[q].k + d); c->st.fused_nodes++; }
+    {
+        timed_scope ts(c, (std::string("mmq_q8_0_skinny") + (ms.size() == 3 ? "_x3" : "_x2") + "_n" + std::to_string(n_total) + "_k" + std::to_string(K)).c_str(), wbytes, true);
+        launch_mmq_q80_skinny_multi(c->stream, (int) ms.size(), mats, (int) K, (int) M, act);
+    }
+    c->st.decode_copy_launches += with_copy != 0;
+    c->st.skinny_launches++;
+    c->st.kernel_launches++;
+    c->st.fused_nodes += ms[0].n_nodes - 1;
+    return ms[0].n_nodes;
 }
 
 // a deferred split-K sum that its designated reader did not pick up after all: run the plain reduce pass now
@@ -1823,7 +1803,7 @@ static int run_node(exec_state & st, int i) {
         }
 
         case GGML_OP_MUL_MAT: {
-            if (mm_cache_image_ok(n) && !buffer_is_split(a->buffer)) {
+            if (mm_runs_on_image(n)) {
                 // K.q over a cache kept in a block format / bf16 (-fa off): the view goes through its f16 image, the product through the f16 kernel
                 tdesc a16 = TD(a), none = TD(a);
                 none.type = GGML_TYPE_F16;  // (launch_kv_images_f16 expands what is not f16: only `a16` here)
@@ -1890,8 +1870,9 @@ static int run_node(exec_state & st, int i) {
                 if (!run_split_mul_mat(c, a, b, n)) return -1;  // column-parallel: broadcast, per-device rows, gather
                 return 1;
             }
-            const bool rowpar = tp_active(c) && buffer_is_rowpar(a->view_src ? a->view_src->buffer : a->buffer);
+            const bool rowpar = tp_active(c) && weight_is_rowpar(a);
             const int64_t M = b->ne[1] * b->ne[2] * b->ne[3];
+            const mm_kind kind = batch_form(c, a, M).kind;  // (the kernel run_mul_mat_q launches for this matrix, unless a SwiGLU or a second addend rides along)
             if (fuse && c->opt.qkv && !rowpar && M == 1 && try_fuse_qkv(st, i)) return 1;
             if (fuse && !rowpar && M <= c->opt.mmvq_max_cols) {
                 // gate/up/SwiGLU: MUL_MAT(Wg,x) MUL_MAT(Wu,x) GLU(g,u)
@@ -1913,8 +1894,7 @@ static int run_node(exec_state & st, int i) {
                     // (columns that belong to the matrix-core kernel — two of a Q4_K / Q6_K matrix — keep it: its store takes ONE addend, so the second ADD stays a
                     // node of its own.  With both addends the product fell back to the mat-vec kernel, and which kernel — which f32 summation order — a mat-mul got
                     // depended on whether its ADDs happened to follow it directly in the node list)
-                    const bool to_mmq = M >= mmq_min_cols_for(c, a->type) && c->opt.mmq_i8 && mmq_i8_supported(a->type, a->ne[0], a->ne[1], M);
-                    if (o2 && !to_mmq) {
+                    if (o2 && kind != MM_I8) {
                         if (!run_mul_mat_q(st, a, nullptr, b, a2, o1, o2)) return -1;
                         c->st.fused_nodes += 2;
                         return 3;
@@ -1924,18 +1904,16 @@ static int run_node(exec_state & st, int i) {
                     return 2;
                 }
             }
-            if (fuse && !rowpar && c->opt.mm_merge && a->type == GGML_TYPE_Q8_0 && mmq_q80_skinny_supported(a->type, a->ne[0], a->ne[1], M)) {
+            if (fuse && !rowpar && c->opt.mm_merge && kind == MM_Q80_SKINNY) {
                 const int used = try_merge_q80_skinny(st, i);
                 if (used != 0) return used;
             }
-            if (fuse && !rowpar && c->opt.mm_merge && M >= mmq_min_cols_for(c, a->type) && c->opt.mmq_i8 && mmq_i8_supported(a->type, a->ne[0], a->ne[1], M)) {
+            if (fuse && !rowpar && c->opt.mm_merge && kind == MM_I8) {
                 const int used = try_merge_mm_batch(st, i);
                 if (used != 0) return used;
             }
-            if (fuse && !rowpar && ((M >= mmq_min_cols_for(c, a->type) && c->opt.mmq_i8 && mmq_i8_supported(a->type, a->ne[0], a->ne[1], M)) ||
-                                    (M >= c->opt.q80_min_cols && mmq_q80_supported(a->type, a->ne[0], a->ne[1], M)) || mmq_q80_skinny_supported(a->type, a->ne[0], a->ne[1], M) ||
-                                    mmq_l32_form(a->type, a->ne[0], a->ne[1], M) != 0)) {
-                // batches: MUL_MAT -> ADD (bias row or residual) rides in the GEMM's store
+            if (fuse && !rowpar && kind != MM_VEC && kind != MM_F16) {
+                // batches: MUL_MAT -> ADD (bias row or residual) rides in the GEMM's store (every matrix-core form but the f16 tiles has one)
                 ggml_tensor * a1 = next(1);
                 const ggml_tensor * o1 = (a1 && single_use(st, n)) ? add_partner(a1, n) : nullptr;
                 if (o1) {
@@ -2112,16 +2090,7 @@ static int run_node(exec_state & st, int i) {
                 rope_params rp{};
                 int rope_m = 0;
                 if (rope && c->rope_tab) {
-                    rp.n_dims = rope->op_params[1];
-                    rp.mode = rope->op_params[2];
-                    rp.n_ctx_orig = rope->op_params[4];
-                    rp.freq_base = ggml_abi_op_param_f32(rope, 5);
-                    rp.freq_scale = ggml_abi_op_param_f32(rope, 6);
-                    rp.ext_factor = ggml_abi_op_param_f32(rope, 7);
-                    rp.attn_factor = ggml_abi_op_param_f32(rope, 8);
-                    rp.beta_fast = ggml_abi_op_param_f32(rope, 9);
-                    rp.beta_slow = ggml_abi_op_param_f32(rope, 10);
-                    memset(rp.sections, 0, sizeof(rp.sections));
+                    rp = rope_params_of(rope, false);
                     rope_m = (int) rope->ne[2];
                     static const bool tab_on = !getenv("GGML_MI355X_ROPE_TABLE") || atoi(getenv("GGML_MI355X_ROPE_TABLE")) != 0;
                     if (!tab_on || rope_m < 1 || rope_m > 64 || rp.n_dims < 2 || rp.n_dims > 256 || (int64_t) rope_m * rp.n_dims > (int64_t) backend_ctx::rope_tab_floats) rope_m = 0;
@@ -2226,17 +2195,7 @@ static int run_node(exec_state & st, int i) {
         }
         case GGML_OP_ROPE: {
             if (fuse && try_fuse_rope_store(st, i)) return 1;
-            rope_params p;
-            p.n_dims = n->op_params[1];
-            p.mode = n->op_params[2];
-            p.n_ctx_orig = n->op_params[4];
-            p.freq_base = ggml_abi_op_param_f32(n, 5);
-            p.freq_scale = ggml_abi_op_param_f32(n, 6);
-            p.ext_factor = ggml_abi_op_param_f32(n, 7);
-            p.attn_factor = ggml_abi_op_param_f32(n, 8);
-            p.beta_fast = ggml_abi_op_param_f32(n, 9);
-            p.beta_slow = ggml_abi_op_param_f32(n, 10);
-            memcpy(p.sections, n->op_params + 11, sizeof(p.sections));
+            const rope_params p = rope_params_of(n, true);
             timed_scope ts(c, "rope", (double) ggml_abi_nbytes(n) * 2);
             launch_rope(s, TD(a), TD(b), n->src[2] ? (const float *) n->src[2]->data : nullptr, TD(n), p);
             c->st.kernel_launches++;
@@ -2324,7 +2283,7 @@ static int run_node(exec_state & st, int i) {
                                 rows_contig(w) && (w->ne[0] % 256) == 0 && !buffer_is_split(w->buffer);
                 if (S > 0 && view && mm && mm->op == GGML_OP_MUL_MAT && mm->src[1] == view && kq && w->ne[0] == n->ne[0] * n->ne[1] && ggml_abi_nelements(view) == w->ne[0] &&
                     use_count(st, view) == 1 && !(view->flags & GGML_TENSOR_FLAG_OUTPUT) && ggml_abi_is_contiguous(mm) && mm->type == GGML_TYPE_F32 &&
-                    !(tp_active(c) && buffer_is_rowpar(w->view_src ? w->view_src->buffer : w->buffer))) {
+                    !(tp_active(c) && weight_is_rowpar(w))) {
                     p.n_splits = S;
                     p.fat = 1;
                     timed_scope ts(c, "flash_attn_fat", (double) (k->ne[1] * k->ne[2] * k->ne[0] * 2 * 2));

@@ -162,6 +162,43 @@ def test_mul_mat_q_matrix_core_variants(backend, H, plog, qt, K, N, M, i8, bn):
 
 
 @pytest.mark.parametrize("qt", [L.Q4_K, L.Q5_K, L.Q6_K])
+def test_f16_tiles_leave_a_bias_add_to_the_mat_vec_passes(backend, H, plog, qt):
+    """Options mmq_i8 = 0 and mmvq_max_cols = 9, nine columns (the narrowest batch the f16-MFMA tile kernel takes, admitted to the mat-vec fusions by the second
+    option): that kernel has no addend in its store, so MUL_MAT -> ADD(bias) runs as passes of the mat-vec kernel with the bias folded in, while the bare MUL_MAT
+    takes the tiles."""
+    K, N, M = 256, 64, 9
+    rng = np.random.default_rng(300 + qt)
+    w = T.rand_weight(qt, K, N, rng)
+    x = (rng.standard_normal((M, K)) * rng.uniform(0.2, 3.0, (M, 1))).astype(np.float32)
+    b = rng.standard_normal(N).astype(np.float32)
+
+    def build(bias):
+        def f(g):
+            r = H.ggml_mul_mat(g.ctx, g.new(qt, [K, N], w), g.new(L.F32, [K, M], x))
+            return H.ggml_add(g.ctx, r, g.new(L.F32, [N], b)) if bias else r
+        return f
+
+    backend.set_option("mmq_i8", 0)
+    backend.set_option("mmvq_max_cols", 9)
+    backend.set_option("timing", 1)
+    try:
+        for bias, prefix in ((True, "mmvq_"), (False, "mmq_")):
+            ref = T.run_case(build(bias), "oracle")
+            backend.timing_report()
+            f0 = backend.stat("fused_nodes")
+            got = T.run_case(build(bias), backend)
+            classes = sorted(backend.timing_report())
+            mmc = [c for c in classes if c.startswith(("mmvq_", "mmq_"))]
+            assert len(mmc) == 1 and mmc[0].startswith(prefix + QNAME[qt]), (bias, classes)
+            assert backend.stat("fused_nodes") - f0 == (1 if bias else 0), (bias, classes)
+            T.compare(f"mul_mat {QNAME[qt]} M={M} mmq_i8=0 bias={bias}", got[0], ref[0], max_nmse=1e-10, log=plog)
+    finally:
+        backend.set_option("mmq_i8", 1)
+        backend.set_option("mmvq_max_cols", 2)
+        backend.set_option("timing", 0)
+
+
+@pytest.mark.parametrize("qt", [L.Q4_K, L.Q5_K, L.Q6_K])
 @pytest.mark.parametrize("M,bias", [(32, False), (12, True), (64, True), (300, False), (512, True)])
 def test_sibling_mul_mats_share_a_launch(backend, H, plog, qt, M, bias):
     """wq / wk / wv (and gate / up) of a batch multiply the same activations: one matrix-core launch over the concatenated row
