@@ -408,7 +408,7 @@ bool launch_attn_nf_list(hipStream_t s, const tdesc & q, const tdesc & k, const 
     if ((mask.type != GGML_TYPE_F16 && mask.type != GGML_TYPE_F32) || mask.ne[0] < k.ne[1] || mask.ne[1] < q.ne[1] || mask.ne[2] != 1 || mask.ne[3] != 1) return false;
     const int G = (int) (q.ne[2] / k.ne[2]);
     if (q8_out && (dq != 1 || (G & 1))) return false;  // Q8_K blocks are head pairs of whole rows
-    static const int groups_on = !getenv("GGML_MI355X_NF_GROUPS") || atoi(getenv("GGML_MI355X_NF_GROUPS")) != 0;
+    static const int groups_on = env_flag("GGML_MI355X_NF_GROUPS", true);
     dim3 grid((unsigned) q.ne[1], (unsigned) k.ne[2], (unsigned) dq);
 #define NF(G_) case G_: hipLaunchKernelGGL(k_attn_nf_list<G_>, grid, dim3(256), (size_t) (G_ * 128 + NF_CAP + G_ * NF_CAP) * 4, s, q, k, v, mask, dst, lists, list_stride, scratch, scale, dq, (q8k_dev *) q8_out, groups_on); return true;
     switch (G) { NF(1) NF(2) NF(3) NF(4) NF(5) NF(6) NF(7) NF(8) default: break; }

@@ -177,7 +177,7 @@ static uploader g_uploaders[GGML_MI355X_MAX_DEVICES];
 // 56.5 GB/s, this engine 55.5 (4 or 8 copy threads; 33 with one) — ROCm 7.2's own pageable path already runs at the PCIe Gen5 rate, a
 // 42.5 GB model is 0.8 s of copying either way.  What the engine still buys is the early return (the loader's next read overlaps the DMA);
 // GGML_MI355X_STAGED_UPLOAD=1 / set_option("staged_upload", 1) turns it on.
-static std::atomic<int> g_staged_upload{[] { const char * e = getenv("GGML_MI355X_STAGED_UPLOAD"); return e ? atoi(e) : 0; }()};
+static std::atomic<int> g_staged_upload{env_int("GGML_MI355X_STAGED_UPLOAD", 0)};
 
 static void par_memcpy(char * dst, const char * src, size_t n, int n_threads) {
     if (n_threads <= 1 || n < ((size_t) 4 << 20)) { memcpy(dst, src, n); return; }
@@ -705,7 +705,7 @@ static ggml_backend_t dev_init_backend(ggml_backend_dev_t dev, const char *) {
         return nullptr;
     }
     {   // every kernel file's code object onto this device now, not in front of the first prompt (kernels.h: MI_TU_TOUCH)
-        static const bool preload = !getenv("GGML_MI355X_PRELOAD") || atoi(getenv("GGML_MI355X_PRELOAD")) != 0;
+        static const bool preload = env_flag("GGML_MI355X_PRELOAD", true);
         static std::mutex pre_mtx;
         static bool preloaded[64] = {false};
         std::lock_guard<std::mutex> lk(pre_mtx);
@@ -722,30 +722,7 @@ static ggml_backend_t dev_init_backend(ggml_backend_dev_t dev, const char *) {
         (void) hipGetLastError();
         c->fa_arrive = nullptr;
     }
-    if (const char * e = getenv("GGML_MI355X_GRAPHS")) c->opt.graphs = atoi(e) != 0;
-    if (const char * e = getenv("GGML_MI355X_FUSION")) c->opt.fusion = atoi(e) != 0;
-    if (const char * e = getenv("GGML_MI355X_PROLOGUE")) c->opt.prologue = atoi(e) != 0;
-    if (const char * e = getenv("GGML_MI355X_QKV")) c->opt.qkv = atoi(e) != 0;
-    if (const char * e = getenv("GGML_MI355X_MMQ_MIN_COLS")) c->opt.mmq_min_cols = atoi(e);
-    if (const char * e = getenv("GGML_MI355X_MMVQ_MAX_COLS")) c->opt.mmvq_max_cols = atoi(e);
-    if (const char * e = getenv("GGML_MI355X_FA_SPLITS")) c->opt.fa_splits = atoi(e);
-    if (const char * e = getenv("GGML_MI355X_FA_WO")) c->opt.fa_wo = atoi(e) != 0;
-    if (const char * e = getenv("GGML_MI355X_SMALL_UPLOADS")) c->opt.small_uploads = atoi(e) != 0;
-    if (const char * e = getenv("GGML_MI355X_SMALL_DOWNLOADS")) c->opt.small_downloads = atoi(e) != 0;
-    if (const char * e = getenv("GGML_MI355X_MMQ_I8")) c->opt.mmq_i8 = atoi(e) != 0;
-    if (const char * e = getenv("GGML_MI355X_MM_MERGE")) c->opt.mm_merge = atoi(e) != 0;
-    if (const char * e = getenv("GGML_MI355X_MMQ_BN")) c->opt.mmq_bn = atoi(e);
-    if (const char * e = getenv("GGML_MI355X_BF16_NT")) c->opt.bf16_nt = atoi(e) != 0;
-    if (const char * e = getenv("GGML_MI355X_BF16_FORM")) c->opt.bf16_form = atoi(e);
-    if (const char * e = getenv("GGML_MI355X_BF16_PREROUND")) c->opt.bf16_preround = atoi(e) != 0;
-    if (const char * e = getenv("GGML_MI355X_BF16_MMV_MAX_COLS")) c->opt.bf16_mmv_max_cols = atoi(e);
-    if (const char * e = getenv("GGML_MI355X_MMQ_SKINNY")) c->opt.mmq_skinny = atoi(e) != 0;
-    if (const char * e = getenv("GGML_MI355X_SKINNY_ROPE")) c->opt.skinny_rope = atoi(e) != 0;
-    if (const char * e = getenv("GGML_MI355X_SKINNY_MIX")) c->opt.skinny_mix = atoi(e) != 0;
-    if (const char * e = getenv("GGML_MI355X_SOFTMAX_MM")) c->opt.softmax_mm = atoi(e) != 0;
-    if (const char * e = getenv("GGML_MI355X_ATTN_NF")) c->opt.attn_nf = atoi(e) != 0;
-    if (const char * e = getenv("GGML_MI355X_FA_SELF_MERGE")) c->opt.fa_self_merge = atoi(e) != 0;
-    if (const char * e = getenv("GGML_MI355X_SS_PARTIALS")) c->opt.ss_partials = atoi(e) != 0;
+    options_from_env(c->opt);
     if (hipMalloc((void **) &c->ss_buf, 256 * sizeof(double)) != hipSuccess) {  // (optional: without it every norm prologue sums its own row)
         (void) hipGetLastError();
         c->ss_buf = nullptr;
@@ -843,41 +820,13 @@ static int api_set_option(ggml_backend_t be, const char * key, const char * valu
     backend_ctx * c = (backend_ctx *) be->context;
     const std::string k = key;
     const int v = atoi(value);
-    if (k == "graphs") c->opt.graphs = v != 0;
-    else if (k == "fusion") c->opt.fusion = v != 0;
-    else if (k == "prologue") c->opt.prologue = v != 0;
-    else if (k == "qkv") c->opt.qkv = v != 0;
-    else if (k == "mmvq_max_cols") c->opt.mmvq_max_cols = v;
-    else if (k == "mmq_min_cols") c->opt.mmq_min_cols = v;
-    else if (k == "mmq_i8") c->opt.mmq_i8 = v != 0;
-    else if (k == "mm_merge") c->opt.mm_merge = v != 0;
-    else if (k == "mmq_bn") c->opt.mmq_bn = v;
-    else if (k == "bf16_form") c->opt.bf16_form = v;
-    else if (k == "bf16_mmv_max_cols") c->opt.bf16_mmv_max_cols = v;
-    else if (k == "bf16_nt") c->opt.bf16_nt = v != 0;
-    else if (k == "bf16_preround") c->opt.bf16_preround = v != 0;
-    else if (k == "mmq_skinny") c->opt.mmq_skinny = v != 0;
-    else if (k == "skinny_rope") c->opt.skinny_rope = v != 0;
-    else if (k == "skinny_mix") c->opt.skinny_mix = v != 0;
-    else if (k == "softmax_mm") c->opt.softmax_mm = v != 0;
-    else if (k == "attn_nf") c->opt.attn_nf = v != 0;
-    else if (k == "fa_self_merge") c->opt.fa_self_merge = v != 0;
-    else if (k == "ss_partials") c->opt.ss_partials = v != 0;
-    else if (k == "tp_p2p") { if (!tp_p2p_enable(c, v != 0)) return -2; }
-    else if (k == "tp_p2p_reset") { if (!tp_p2p_reset(c)) return -2; }
-    else if (k == "fa_splits") c->opt.fa_splits = v;
-    else if (k == "fa_wo") c->opt.fa_wo = v != 0;
-    else if (k == "small_uploads") c->opt.small_uploads = v != 0;
-    else if (k == "small_downloads") c->opt.small_downloads = v != 0;
-    else if (k == "timing") c->opt.timing = v != 0;
-    else if (k == "exec_update") c->opt.exec_update = v;
-    else if (k == "shadow_capture") c->opt.shadow_capture = v;
-    else if (k == "q80_min_cols") c->opt.q80_min_cols = v;
-    else if (k == "decode_copy") c->opt.decode_copy = v != 0;
-    else if (k == "decode_copy_headroom_gib") c->opt.decode_copy_headroom_gib = v;
-    else if (k == "clear_failure") { if (v) clear_hip_failure(); }
-    else if (k == "staged_upload") g_staged_upload.store(v != 0);
-    else return -1;
+    if (!options_set(c->opt, key, v)) {  // no row of MI_OPTIONS (options.h): the keys that are no field of c->opt
+        if (k == "tp_p2p") { if (!tp_p2p_enable(c, v != 0)) return -2; }
+        else if (k == "tp_p2p_reset") { if (!tp_p2p_reset(c)) return -2; }
+        else if (k == "clear_failure") { if (v) clear_hip_failure(); }
+        else if (k == "staged_upload") g_staged_upload.store(v != 0);
+        else return -1;
+    }
     HIP_SOFT(hipStreamSynchronize(c->stream));
     free_graph_cache(c);
     return 0;
@@ -886,45 +835,9 @@ static int64_t api_get_stat(ggml_backend_t be, const char * key) {
     if (!be_is_ours(be)) return -1;
     backend_ctx * c = (backend_ctx *) be->context;
     const std::string k = key;
-    if (k == "graph_launches") return c->st.graph_launches;
-    if (k == "graph_captures") return c->st.graph_captures;
-    if (k == "eager_graphs") return c->st.eager_graphs;
-    if (k == "kernel_launches") return c->st.kernel_launches;
-    if (k == "fused_nodes") return c->st.fused_nodes;
-    if (k == "allreduces") return c->st.allreduces;
-    if (k == "ss_handoffs") return c->st.ss_handoffs;
-    if (k == "fa_list_launches") return c->st.fa_list_launches;
-    if (k == "fa_form") return c->st.fa_form;
-    if (k == "nf_mma_chains") return c->st.nf_mma_chains;
-    if (k == "p2p_allreduces") return c->st.p2p_allreduces;
-    if (k == "p2p_timeouts") return tp_p2p_timeouts(c);
-    if (k == "step_heads") return c->st.step_heads;
-    if (k == "elided_conts") return c->st.elided_conts;
-    if (k == "decode_copy_tensors") return c->st.decode_copy_tensors;
-    if (k == "decode_copy_bytes") return c->st.decode_copy_bytes;
-    if (k == "decode_copy_launches") return c->st.decode_copy_launches;
-    if (k == "graph_exec_update_failures") return c->st.graph_exec_update_failures;
-    if (k == "graph_evictions") return c->st.graph_evictions;
+    if (const int64_t * p = stats_find(c->st, key)) return *p;
     if (k == "graph_cache_size") return (int64_t) c->graphs.size();
-    if (k == "graph_launch_host_ns") return c->st.graph_launch_host_ns;
-    if (k == "kernel_downloads") return c->st.kernel_downloads;
-    if (k == "kv_image_nodes") return c->st.kv_image_nodes;
-    if (k == "kv_native_nodes") return c->st.kv_native_nodes;
-    if (k == "graph_key_host_ns") return c->st.graph_key_host_ns;
-    if (k == "graph_compute_host_ns") return c->st.graph_compute_host_ns;
-    if (k == "graph_key_fast_hits") return c->st.graph_key_fast_hits;
-    if (k == "graph_key_collisions") return c->st.graph_key_collisions;
-    if (k == "graph_early_captures") return c->st.graph_early_captures;
-    if (k == "graph_shadow_captures") return c->st.graph_shadow_captures;
-    if (k == "graph_capture_walk_ns") return c->st.graph_capture_walk_ns;
-    if (k == "graph_exec_update_ns") return c->st.graph_exec_update_ns;
-    if (k == "graph_shadow_eager_ns") return c->st.graph_shadow_eager_ns;
-    if (k == "graph_exec_updates") return c->st.graph_exec_updates;
-    if (k == "skinny_launches") return c->st.skinny_launches;
-    if (k == "mmid_launches") return c->st.mmid_launches;
-    if (k == "wide_launches") return c->st.wide_launches;
-    if (k == "tiled_launches") return c->st.tiled_launches;
-    if (k == "rope_epilogues") return c->st.rope_epilogues;
+    if (k == "p2p_timeouts") return tp_p2p_timeouts(c);
     if (k.rfind("ip_", 0) == 0) return ip_stat(c, key);
     if (k == "staged_upload_bytes") return (int64_t) g_uploaders[c->device].bytes;
     if (k == "staged_upload_us") return (int64_t) (g_uploaders[c->device].seconds * 1e6);
@@ -1001,7 +914,7 @@ static void init_reg() {
         n = 0;
     }
     // GGML_MI355X_FAKE_DEVICES=N: N logical devices per physical one (tests of the multi-device paths on a single-GPU box)
-    const int fake = getenv("GGML_MI355X_FAKE_DEVICES") ? std::max(1, atoi(getenv("GGML_MI355X_FAKE_DEVICES"))) : 1;
+    const int fake = std::max(1, env_int("GGML_MI355X_FAKE_DEVICES", 1));
     for (int ii = 0; ii < n * fake && (int) g_reg_ctx.devices.size() < GGML_MI355X_MAX_DEVICES; ++ii) {
         const int i = ii / fake;
         hipDeviceProp_t prop;

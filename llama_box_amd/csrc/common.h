@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "../../include/ggml_mi355x.h"
+#include "options.h"  // struct options, struct stats, env_flag / env_int / env_present
 
 #define MI_LOG(level, ...)                                    \
     do {                                                      \
@@ -113,82 +114,6 @@ struct q81_dev {
 static_assert(sizeof(q81_dev) == 40, "q81_dev");
 
 struct backend_ctx;
-
-#define MI_BF16_MMV_MAX_COLS 8  // default hand-over from the bf16 streaming kernel's multi-column form to the 16 x 16 tiles (option bf16_mmv_max_cols)
-#define MI_BF16_NT 1            // default load policy of the bf16 streaming kernel: non-temporal (option bf16_nt / GGML_MI355X_BF16_NT)
-#define MI_BF16_PREROUND 1      // default of option bf16_preround: on (measured 1.25 - 1.45 x faster at 512 and 2048 columns: profiles/r09_bf16_bench.txt)
-struct options {
-    bool graphs = true;        // hipGraph capture + replay of repeated graphs
-    bool fusion = true;        // node fusion (norm+mul, mul_mat+add, ...)
-    bool prologue = true;      // fold RMS_NORM / activation quantisation into the mat-vec prologue
-    bool qkv = true;           // fused Q/K/V + rope + cache store launch
-    int mmvq_max_cols = 2;     // widest batch that takes the mat-vec fusions (gate/up/SwiGLU, +bias +residual in one launch); from three columns on the
-                               // skinny matrix-core kernel + its separate SwiGLU launch is faster (-np 8 step 4.06 -> 3.45 ms, -np 3 3.77 -> 3.35)
-    int mmq_min_cols = 3;      // batches at least this wide run on the matrix cores (measured, ms/step matrix cores vs multi-column mat-vec: 3 columns 4.1 / 4.4, 4: 3.9 / 4.2, 8: 4.4 / 5.7; 2 columns: 3.6 / 3.1)
-    bool mmq_i8 = true;        // Q4_K/Q5_K batches on the int8 matrix cores (mmq_i8.hip) instead of the f16 variant (mmq.hip)
-    bool mm_merge = true;      // batches: sibling mat-muls over the same activations (wq/wk/wv, gate/up) as one launch
-    bool ss_partials = true;    // residual-stream mat-vecs leave the sum of squares of their result for the next RMS_NORM prologue (GGML_MI355X_SS_PARTIALS=0: off)
-    bool fa_self_merge = false; // split attention (decode): the last split workgroup merges the partial records, no combine launch.  Off: measured
-                               // one token, n_kv 2100: 16.5 us against 7.6 + 5.0 for split + combine (record write-through, counter and re-read are a longer
-                               // dependent chain than a launch); -np 32: 18.3 against 19.6 us per layer (4.45 vs 4.49 ms per step)
-    bool attn_nf = true;       // -np decode steps on the non-flash path: K.q -> SOFT_MAX -> V^T.p as one launch over the tokens' visible-cell lists (attn_nf.hip)
-    bool softmax_mm = true;    // decode on the non-flash path: SOFT_MAX folded into the V^T.p product that reads it (mmf.hip)
-    bool skinny_rope = true;   // -np decode steps: ROPE(q), ROPE(k) and both KV-cache stores in the epilogue of the skinny QKV launch(es)
-    bool skinny_mix = true;    // -np decode steps: sibling mat-muls stored in two K-quant formats (Q4_K wq / wk + Q6_K wv) share one skinny launch
-    bool mmq_skinny = true;    // 2..32 columns: weight-streaming matrix-core kernel (mmq_skinny.hip) instead of the tiled GEMM
-    int mmq_bn = 0;            // force the weight-panel height of mmq_i8 (64 / 128); 0 = pick by grid size
-    // bf16 weight matrices (mmbf.hip)
-    int bf16_form = -1;        // -1: routed; MI_BF16_DOT .. MI_BF16_MMA: that form wherever it can serve the operands (measurements and tests)
-    int bf16_mmv_max_cols = MI_BF16_MMV_MAX_COLS;  // widest batch on the streaming kernel; wider ones go to the matrix cores
-    int bf16_nt = MI_BF16_NT;  // non-temporal weight loads in the streaming kernel
-    int bf16_preround = MI_BF16_PREROUND;  // batches on the 32 x 32 tiles: src1 rounded to bf16 once into scratch instead of in every workgroup's loop
-    int fa_splits = 0;         // 0 = auto
-    bool fa_wo = false;        // decode: attention as few fat splits whose merge is the wo mat-vec's prologue (no combine launch).  Correct and
-                               // tested, OFF by default: a KV trip of the lane-parallel kernel is a ~4 us dependent chain, so 9 splits of 2
-                               // trips (12.0 us) + the merging prologue (wo 6.8 -> 10.4 us) lose to 36 one-trip splits + combine (13.6 + 6.8)
-    bool small_uploads = true; // set_tensor_async of <= 64 KiB: pinned ring + copy kernel instead of a blit
-    bool small_downloads = true; // get_tensor_async of <= 8 MiB into this backend's pinned host buffer type: a copy kernel instead of a blit
-    bool timing = false;       // hipEvent-bracket kernel classes (bench only; disables graphs)
-    int decode_copy_headroom_gib = 2;  // a buffer's decode copy is made only while this much device memory stays free beside it (tests raise it to force the fallback)
-    bool decode_copy = [] { const char * e = getenv("GGML_MI355X_DECODE_COPY"); return e ? atoi(e) != 0 : true; }();  // batch-1 mat-vecs read the plane-layout copy of their weights
-    int exec_update = [] { const char * e = getenv("GGML_MI355X_EXEC_UPDATE"); return e ? atoi(e) : 1; }();  // patch the predecessor's executable graph at a capture at
-    int shadow_capture = [] { const char * e = getenv("GGML_MI355X_SHADOW_CAPTURE"); return e ? atoi(e) : 1; }();  // a capture at first sighting runs BEHIND the step's own eager launches
-    int q80_min_cols = [] { const char * e = getenv("GGML_MI355X_Q80_MIN_COLS"); return e ? atoi(e) : 33; }();  // Q8_0 weights: batches of at least this many columns take the matrix-core GEMM (mmq_q80.hip), smaller ones 8-column mat-vec passes
-                               // first sighting (graph.cpp); 2 = run the update and treat it as failed (tests)
-};
-
-struct stats {
-    int64_t graph_launches = 0, graph_captures = 0, eager_graphs = 0, kernel_launches = 0, fused_nodes = 0, allreduces = 0;
-    int64_t p2p_allreduces = 0;        // row-parallel sums served by the one-shot peer-to-peer kernel (tp_p2p.hip) instead of RCCL
-    int64_t ss_handoffs = 0;           // RMS_NORM prologues that took the sum of squares from the producing mat-vec's partial sums
-    int64_t skinny_launches = 0;       // mat-muls of 2..32 columns served by the weight-streaming matrix-core kernel
-    int64_t mmid_launches = 0;         // MUL_MAT_ID nodes served by the expert mat-vec launch (mmid.hip), one launch a node
-    int64_t wide_launches = 0;         // prompt-batch mat-muls served by its wide form
-    int64_t tiled_launches = 0;        // batch mat-muls served by the LDS-tiled int8 GEMM (mmq_i8.hip)
-    int64_t nf_mma_chains = 0;         // non-flash K.q -> SOFT_MAX -> V^T.p chains of a prompt micro-batch served by the two-pass matrix-core kernel (round 4)
-    int64_t fa_form = 0;               // kernels.h fa_form_code of the last FLASH_ATTN_EXT node of the graph computed last (0: it had none)
-    int64_t fa_list_launches = 0;      // FLASH_ATTN_EXT nodes served over per-token position lists (2..32 tokens; 33..256 when the mask is known to be sparse)
-    int64_t rope_epilogues = 0;        // batches whose rope + KV-cache stores rode in the skinny QKV launches
-    int64_t graph_launch_host_ns = 0;  // host time spent inside hipGraphLaunch (replays only)
-    int64_t graph_key_host_ns = 0;     // replays only: host time from entering graph_compute to calling hipGraphLaunch (recognising the graph)
-    int64_t graph_compute_host_ns = 0; // host time inside graph_compute, all paths
-    int64_t graph_key_fast_hits = 0;   // replays recognised by comparing against the graph replayed last (no key built, no hash)
-    int64_t kv_native_nodes = 0;       // ... and those whose K / V in such a type were read in place by the lane-parallel kernel's DQ form
-    int64_t kv_image_nodes = 0;        // FLASH_ATTN_EXT nodes whose K / V (kept in q4_0, q4_1, q5_0, q5_1, iq4_nl, bf16, f32 ...) were read through an f16 image
-    int64_t kernel_downloads = 0;      // get_tensor_async calls served by a copy kernel writing mapped pinned memory
-    int64_t graph_early_captures = 0;  // graphs captured at their FIRST sighting (same step as the one replayed last, over a grown cache)
-    int64_t graph_shadow_captures = 0; // ... of which the capture ran behind the step's own eager launches (the GPU busy meanwhile) and serves the NEXT step
-    int64_t graph_capture_walk_ns = 0, graph_exec_update_ns = 0, graph_shadow_eager_ns = 0;  // host time of: the walk into a capture (begin..end), hipGraphExecUpdate / instantiate, a shadow capture's eager walk
-    int64_t graph_exec_updates = 0;    // ... of them, served by patching the predecessor's executable graph (hipGraphExecUpdate) instead of instantiating
-    int64_t decode_copy_tensors = 0;   // weight matrices repacked into the decode copy by this backend instance ...
-    int64_t decode_copy_bytes = 0;     // ... and their bytes
-    int64_t decode_copy_launches = 0;  // mat-vec / fused Q/K/V launches that streamed a decode copy
-    int64_t elided_conts = 0;          // cont(permute(kqv)) copies of a one-token non-flash attention whose bytes the producing launch wrote in place (round 6)
-    int64_t step_heads = 0;            // decode-step heads served by one launch: GET_ROWS + mask cast + rotary table (ops.hip: k_step_head)
-    int64_t graph_exec_update_failures = 0; // ... and updates that failed: the predecessor's (possibly half-patched) executable graph is destroyed, both entries start over
-    int64_t graph_evictions = 0;       // cache entries dropped because they had not been used for 256 graphs
-    int64_t graph_key_collisions = 0;  // two different graph keys with one hash (each keeps its own entry)
-};
 
 struct tp_state;      // tp.cpp
 struct split_helper;  // split.cpp

@@ -26,7 +26,7 @@ namespace mi355x {
 // multi-head attention — G = 1 — as 2: the surplus head slots read the group's last head with a zero query and are never stored — Llama-3.2-3B is 24 / 8 heads,
 // Qwen2.5-1.5B 12 / 2, Qwen2-7B 28 / 4, Llama-2-7B 32 / 32: 467 -> 523 tok/s against the generic kernel, profiles/r06_other_families.txt)
 static inline bool fa_g_ok(const int64_t G) {
-    static const int g_min = getenv("GGML_MI355X_FA_G_MIN") ? atoi(getenv("GGML_MI355X_FA_G_MIN")) : 1;  // (2: multi-head attention back on the generic kernel)
+    static const int g_min = env_int("GGML_MI355X_FA_G_MIN", 1);  // (2: multi-head attention back on the generic kernel)
     return G >= g_min && G <= 8;
 }
 static inline int fa_gg(const int64_t G) { return G <= 2 ? 2 : (G <= 4 ? 4 : 8); }
@@ -1101,7 +1101,7 @@ __global__ void __launch_bounds__(256) k_fattn_combine_rows(const float * __rest
 
 // is the combine pass of this shape served by the row-parallel kernel (which also quantises for free)?
 bool fattn_combine_rows_applies(int D, int64_t n_q, int64_t n_head, int64_t n_batch, int n_splits, const float * sinks) {
-    static const bool rows_on = !getenv("GGML_MI355X_FA_COMBINE_ROWS") || atoi(getenv("GGML_MI355X_FA_COMBINE_ROWS")) != 0;
+    static const bool rows_on = env_flag("GGML_MI355X_FA_COMBINE_ROWS", true);
     const int64_t n_rows = n_batch * n_q * n_head;
     return rows_on && !sinks && D == 128 && n_splits >= 2 && n_splits <= 8 && n_rows >= 2048 && n_rows < (1 << 30);
 }
@@ -1135,7 +1135,7 @@ void launch_flash_attn_combine(hipStream_t s, int D, const float * ws, const flo
 }
 
 bool fattn_prefers_lists(const tdesc & q, const tdesc * mask, int mask_sparse) {
-    static const bool on = !getenv("GGML_MI355X_FA_SPARSE_LISTS") || atoi(getenv("GGML_MI355X_FA_SPARSE_LISTS")) != 0;
+    static const bool on = env_flag("GGML_MI355X_FA_SPARSE_LISTS", true);
     return on && mask != nullptr && q.ne[1] >= fattn_mma_min_q() && q.ne[1] <= 256 && mask_sparse != 0;
 }
 int fattn_pick_splits(const tdesc & q, const tdesc & k, const tdesc * mask, int mask_sparse) {
@@ -1281,7 +1281,7 @@ __global__ void __launch_bounds__(256) k_fattn_pos_scan(const tdesc mask, const 
 int fattn_list_tile(const tdesc & q, const tdesc & k, const tdesc * mask, const fattn_params & p, size_t lists_bytes) {
     const int64_t n_q = q.ne[1];
     const int G = k.ne[2] > 0 ? (int) (q.ne[2] / k.ne[2]) : 0;
-    static const bool on = !getenv("GGML_MI355X_FA_LIST") || atoi(getenv("GGML_MI355X_FA_LIST")) != 0;
+    static const bool on = env_flag("GGML_MI355X_FA_LIST", true);
     const bool d64 = k.ne[0] == 64 && k.type == GGML_TYPE_F16;  // (round 6: the eight-lane-row form of the kernel; fattn_q8_out_ok refuses head_dim 64, arrival counters are not used)
     if (!on || n_q < 2 || (n_q >= fattn_mma_min_q() && !fattn_prefers_lists(q, mask, p.mask_sparse)) || !mask || q.ne[3] != 1 || mask->ne[3] != 1 || (k.ne[0] != 128 && !d64)) return 0;
     if (p.logit_softcap != 0.0f || p.max_bias != 0.0f || !fa_g_ok(G) || p.n_splits < 1) return 0;
@@ -1300,7 +1300,7 @@ void launch_fattn_tile_scan(hipStream_t s, const tdesc & mask, int n_q, int n_kv
 // one of the integer-level formats, 2-byte-aligned strides; everything else (iq4_nl, bf16, f32, mixed pairs, head_dim 64) goes through the image
 static bool dq_type_ok(int t) { return t == GGML_TYPE_Q4_0 || t == GGML_TYPE_Q4_1 || t == GGML_TYPE_Q5_0 || t == GGML_TYPE_Q5_1 || t == GGML_TYPE_IQ4_NL || t == GGML_TYPE_BF16; }
 bool fattn_native_kv_ok(const tdesc & q, const tdesc & k, const tdesc & v, const fattn_params & p) {
-    static const bool on = !getenv("GGML_MI355X_FA_NATIVE_KV") || atoi(getenv("GGML_MI355X_FA_NATIVE_KV")) != 0;
+    static const bool on = env_flag("GGML_MI355X_FA_NATIVE_KV", true);
     if (!on || !dq_type_ok(k.type) || v.type != k.type || k.ne[0] != 128 || v.ne[0] != 128 || k.ne[2] <= 0 || q.ne[2] % k.ne[2] != 0) return false;
     const int G = (int) (q.ne[2] / k.ne[2]);
     if (!fa_g_ok(G) || p.logit_softcap != 0.0f || p.max_bias != 0.0f || q.ne[1] > 32 || p.n_splits < 1) return false;
@@ -1384,7 +1384,7 @@ void launch_flash_attn(hipStream_t s, const tdesc & q, const tdesc & k, const td
         }
         // several query tokens with a mask: skip the KV trips a token cannot see — needs splits of at most 32 trips
         const int per = ((geo.n_kv + geo.n_splits - 1) / geo.n_splits + 63) / 64 * 64;
-        static const bool skip_on = !getenv("GGML_MI355X_FA_SKIP") || atoi(getenv("GGML_MI355X_FA_SKIP")) != 0;
+        static const bool skip_on = env_flag("GGML_MI355X_FA_SKIP", true);
         // p.lists set: the caller has run (or re-used) k_fattn_pos_scan for this mask (fattn_list_tile() said the list form applies)
         const bool list = p.lists != nullptr;
         const int lstride = geo.n_kv + 1;
@@ -1393,8 +1393,8 @@ void launch_flash_attn(hipStream_t s, const tdesc & q, const tdesc & k, const td
                           (mask->nb[3] % 8) == 0 && ((uintptr_t) mask->data & 7) == 0 && geo.n_splits > 1;
         // one decode token over an f16 cache: eight waves per workgroup (a trip covers 128 cells: splits of up to 128 cells are ONE trip)
         // (measured, 2048-token context, 24 splits: 13.45 -> 12.6 us per layer for both launches, 480.7 -> 488.5 tok/s; profiles/r03_decode_ab_fa_wv8.txt)
-        static const int wv8 = getenv("GGML_MI355X_FA_WV8") ? atoi(getenv("GGML_MI355X_FA_WV8")) : 1;
-        static const int list_wv8 = getenv("GGML_MI355X_FA_LIST_WV8") ? atoi(getenv("GGML_MI355X_FA_LIST_WV8")) : 0;
+        static const int wv8 = env_int("GGML_MI355X_FA_WV8", 1);
+        static const int list_wv8 = env_int("GGML_MI355X_FA_LIST_WV8", 0);
         // n_splits > 1: the last split workgroup of a (token, kv head) merges the records itself when the caller gave arrival counters
         // (one launch instead of two); Q8_K output needs whole head pairs inside a kv group.  merge2 (round 4): the one-round-trip merge,
         // for the plain form (no lists, no trip skipping) with f32 output and at most 32 splits, on four or eight waves
@@ -1470,7 +1470,7 @@ void launch_flash_attn(hipStream_t s, const tdesc & q, const tdesc & k, const td
     }
     // one decode token at head_dim 64 over an f16 cache (round 6): the lane-parallel kernel in its eight-lane-row form, records + combine pass
     // (generic kernel: 14.9 us per layer for TinyLlama at a 600-cell context; profiles/r06_secondary_kernel_stats.txt)
-    static const bool dec64_on = !getenv("GGML_MI355X_FA_DEC64") || atoi(getenv("GGML_MI355X_FA_DEC64")) != 0;
+    static const bool dec64_on = env_flag("GGML_MI355X_FA_DEC64", true);
     if (dec64_on && D == 64 && k.type == GGML_TYPE_F16 && v.type == GGML_TYPE_F16 && (geo.n_q == 1 || (p.lists && q.ne[3] == 1)) && p.logit_softcap == 0.0f && p.max_bias == 0.0f && fa_g_ok(G) &&
         (q.nb[1] % 16) == 0 && (q.nb[2] % 16) == 0 && ((uintptr_t) q.data & 15) == 0 && (k.nb[1] % 16) == 0 && (v.nb[1] % 16) == 0 && (k.nb[2] % 16) == 0 && (v.nb[2] % 16) == 0 &&
         ((uintptr_t) k.data & 15) == 0 && ((uintptr_t) v.data & 15) == 0 && p.q8_out == nullptr) {

@@ -656,7 +656,7 @@ bool launch_flash_attn_mma(hipStream_t s, const tdesc & q, const tdesc & k, cons
 
 // ---- the non-flash chain of a prompt micro-batch (k_attn_nf_mma): applicability, workspace, launch
 bool attn_nf_mma_applies(const tdesc & q, const tdesc & k, const tdesc & vt, const tdesc & mask) {
-    static const bool on = !getenv("GGML_MI355X_ATTN_NF_MMA") || atoi(getenv("GGML_MI355X_ATTN_NF_MMA")) != 0;
+    static const bool on = env_flag("GGML_MI355X_ATTN_NF_MMA", true);
     const int64_t D = k.ne[0];
     if (!on || D != 128 || q.ne[1] < fattn_mma_min_q() || q.ne[3] != 1 || k.ne[3] != 1 || vt.ne[3] != 1 || k.type != GGML_TYPE_F16 || vt.type != GGML_TYPE_F16 || q.type != GGML_TYPE_F32 ||
         mask.type != GGML_TYPE_F32)

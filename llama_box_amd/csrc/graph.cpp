@@ -538,10 +538,13 @@ static int graph_use_count(const ggml_cgraph * g, const ggml_tensor * t) {
 }
 // (cos, sin) per (token, rotation pair) of the batch at `pos` (ops.hip: k_rope_table), valid for this execution of the graph: every
 // layer rotates with the same positions and parameters, so the chain of multiplies and the accurate cosf / sinf run once per graph run
+// process-wide switches that two places ask for
+static bool rope_table_on() { static const bool on = env_flag("GGML_MI355X_ROPE_TABLE", true); return on; }
+static bool q80_producers_on() { static const bool on = env_flag("GGML_MI355X_Q80_PRODUCERS", true); return on; }
+
 static const float * ensure_rope_table(exec_state & st, const int32_t * pos, const float * ff, const rope_params & p, int M) {
     backend_ctx * c = st.c;
-    static const bool on = !getenv("GGML_MI355X_ROPE_TABLE") || atoi(getenv("GGML_MI355X_ROPE_TABLE")) != 0;
-    if (!on || !c->rope_tab || M < 1 || (int64_t) M * p.n_dims > (int64_t) backend_ctx::rope_tab_floats) return nullptr;
+    if (!rope_table_on() || !c->rope_tab || M < 1 || (int64_t) M * p.n_dims > (int64_t) backend_ctx::rope_tab_floats) return nullptr;
     if (st.rope_tab_pos != (const void *) pos || st.rope_tab_ff != (const void *) ff || st.rope_tab_m != M || memcmp(&st.rope_tab_p, &p, sizeof(rope_params)) != 0) {
         launch_rope_table(c->stream, pos, ff, p, M, c->rope_tab);
         c->st.kernel_launches++;
@@ -678,7 +681,7 @@ static bool run_mul_mat_q(exec_state & st, const ggml_tensor * w, const ggml_ten
     auto dn = st.deferred.find(b);
     const bool pro_norm = dn != st.deferred.end();
     const bool pro_fa = st.fa_wo.b == b && st.fa_wo.part != nullptr;  // (set by the FLASH_ATTN_EXT node after checking this very mat-vec)
-    static const bool dbg_no_pro_f32 = getenv("GGML_MI355X_DBG_NO_PRO_F32") != nullptr;
+    static const bool dbg_no_pro_f32 = env_present("GGML_MI355X_DBG_NO_PRO_F32");
     // (never when the result recycles the activation row's block — the GLU node of a fused gate / up / SwiGLU triple is placed after the row's last reader: a
     // workgroup that finishes early would overwrite x while a late one's prologue still reads it; the row is then quantised by its own launch, as for batches)
     const bool pro_f32 = !dbg_no_pro_f32 && !pro_norm && !pro_fa && c->opt.fusion && c->opt.prologue && kquant && M == 1 && b->type == GGML_TYPE_F32 && b->nb[0] == 4 && (((uintptr_t) b->data) & 15) == 0 &&
@@ -751,7 +754,7 @@ static bool run_mul_mat_q(exec_state & st, const ggml_tensor * w, const ggml_ten
         return true;
     }
     // the prompt GEMM over Q8_0 weights reads both operands in panel order when the weights have their panel copy (GGML_MI355X_Q80_GEMM_PANELS=0: as before round 6)
-    static const bool gemm_panels = !getenv("GGML_MI355X_Q80_GEMM_PANELS") || atoi(getenv("GGML_MI355X_Q80_GEMM_PANELS")) != 0;
+    static const bool gemm_panels = env_flag("GGML_MI355X_Q80_GEMM_PANELS", true);
     const uint8_t * q80_gemm_wp = (form.kind == MM_Q80_GEMM && gemm_panels) ? q80_panel_copy(c, w) : nullptr;
     const void * act = quantized_src1(st, b, (form.kind == MM_Q80_SKINNY || q80_gemm_wp) ? MI_ACT_Q80_PANEL : w->type);
     if (form.kind == MM_Q80_SKINNY) {  // 9 .. 32 columns of a -np decode step (round 6)
@@ -881,7 +884,7 @@ struct qkv_chain {
 };
 // the block-format / bf16 cache-row stores ride in the fused Q/K/V launch (round 6); GGML_MI355X_QKV_KV_STORE=0: the separate SET_ROWS launch of round 5 (A/B)
 static bool qkv_kv_store_on() {
-    static const bool on = !getenv("GGML_MI355X_QKV_KV_STORE") || atoi(getenv("GGML_MI355X_QKV_KV_STORE")) != 0;
+    static const bool on = env_flag("GGML_MI355X_QKV_KV_STORE", true);
     return on;
 }
 // follows mm -> [ADD bias] -> (RESHAPE)* -> [ROPE] -> (RESHAPE)* -> [SET_ROWS]; stops at the first consumer it cannot absorb
@@ -1758,7 +1761,7 @@ static int run_node(exec_state & st, int i) {
             if (fuse && m && m->op == GGML_OP_MUL && single_use(st, n) && m->type == GGML_TYPE_F32 && m->nb[0] == 4) {
                 const ggml_tensor * w = m->src[0] == n ? m->src[1] : (m->src[1] == n ? m->src[0] : nullptr);
                 if (w && w->type == GGML_TYPE_F32 && ggml_abi_is_contiguous(w) && w->ne[0] == n->ne[0] && ggml_abi_nelements(w) == w->ne[0] && same_shape(m, n)) {
-                    static const bool dbg_no_defer = getenv("GGML_MI355X_DBG_NO_DEFER_NORM") != nullptr;
+                    static const bool dbg_no_defer = env_present("GGML_MI355X_DBG_NO_DEFER_NORM");
                     static const char * dbg_only = getenv("GGML_MI355X_DBG_DEFER_ONLY");
                     if (c->opt.prologue && !dbg_no_defer && (!dbg_only || strstr(m->name, dbg_only)) && can_defer_norm(st, i, n, m, a, w)) {
                         st.deferred[m] = {a, w, ggml_abi_op_param_f32(n, 0), m};
@@ -1778,8 +1781,7 @@ static int run_node(exec_state & st, int i) {
                         c->st.fused_nodes += 2;
                         return 2;
                     }
-                    static const bool q80_producers = !getenv("GGML_MI355X_Q80_PRODUCERS") || atoi(getenv("GGML_MI355X_Q80_PRODUCERS")) != 0;
-                    if (q80_producers && c->opt.prologue && ggml_abi_nrows(m) >= 9 && st.sk_dst != a && rms_norm_q80_panel_ok(TD(a), (const float *) w->data) && q80_panel_consumers_only(st, i + 1, m)) {
+                    if (q80_producers_on() && c->opt.prologue && ggml_abi_nrows(m) >= 9 && st.sk_dst != a && rms_norm_q80_panel_ok(TD(a), (const float *) w->data) && q80_panel_consumers_only(st, i + 1, m)) {
                         timed_scope ts(c, "rms_norm_mul_quantize_q8_0", (double) ggml_abi_nbytes(a));
                         launch_rms_norm_mul_q80_panel(s, TD(a), ggml_abi_op_param_f32(n, 0), (const float *) w->data, (char *) c->ws + st.act_off);
                         mark_q8_cache(st, m, MI_ACT_Q80_PANEL);
@@ -1935,7 +1937,7 @@ static int run_node(exec_state & st, int i) {
                 // for the RMS_NORM prologue that reads the residual stream next)
                 ggml_tensor * a1 = next(1);
                 const ggml_tensor * o1 = (fuse && a1 && single_use(st, n)) ? add_partner(a1, n) : nullptr;
-                static const bool dbg_no_ar_fused = getenv("GGML_MI355X_DBG_NO_AR_FUSED") != nullptr;
+                static const bool dbg_no_ar_fused = env_present("GGML_MI355X_DBG_NO_AR_FUSED");
                 if (o1 && same_shape(o1, n) && !dbg_no_ar_fused) {  // (the ADD may recycle the block of either operand: every thread reads its own elements before it writes them)
                     int ssn = 0;
                     const bool want_ss = c->opt.ss_partials && c->ss_buf != nullptr && M == 1;
@@ -2026,8 +2028,7 @@ static int run_node(exec_state & st, int i) {
                 c->st.fused_nodes++;
                 return 1;
             }
-            static const bool q80_producers = !getenv("GGML_MI355X_Q80_PRODUCERS") || atoi(getenv("GGML_MI355X_Q80_PRODUCERS")) != 0;
-            if (q80_producers && fuse && c->opt.prologue && ggml_abi_nrows(n) >= 9 && swiglu_q80_panel_ok(TD(a), b ? &bd : nullptr, n->ne[0], n->op_params[1]) && q80_panel_consumers_only(st, i, n)) {
+            if (q80_producers_on() && fuse && c->opt.prologue && ggml_abi_nrows(n) >= 9 && swiglu_q80_panel_ok(TD(a), b ? &bd : nullptr, n->ne[0], n->op_params[1]) && q80_panel_consumers_only(st, i, n)) {
                 timed_scope ts(c, "swiglu_quantize_q8_0", (double) ggml_abi_nbytes(n) * 2);
                 launch_swiglu_q80_panel(s, TD(a), b ? &bd : nullptr, n->ne[0], n->op_params[1], (char *) c->ws + st.act_off);
                 mark_q8_cache(st, n, MI_ACT_Q80_PANEL);
@@ -2061,7 +2062,7 @@ static int run_node(exec_state & st, int i) {
             // the fused Q/K/V launches of every layer read are independent of each other — one launch instead of three at the dependent-launch floor.  The cast is
             // hoisted over the nodes between only when its result's memory is not touched by any of them; the table is the one ensure_rope_table would build at the
             // first fused Q/K/V launch (same positions, parameters, token count: it then finds it valid), and is simply rebuilt there if the guess was wrong
-            static const bool head_on = !getenv("GGML_MI355X_STEP_HEAD") || atoi(getenv("GGML_MI355X_STEP_HEAD")) != 0;
+            static const bool head_on = env_flag("GGML_MI355X_STEP_HEAD", true);
             const int64_t n_rows = b->ne[0] * b->ne[1] * b->ne[2];
             if (head_on && fuse && !c->opt.timing && n_rows <= 64) {
                 const ggml_tensor * cast = nullptr;
@@ -2092,8 +2093,7 @@ static int run_node(exec_state & st, int i) {
                 if (rope && c->rope_tab) {
                     rp = rope_params_of(rope, false);
                     rope_m = (int) rope->ne[2];
-                    static const bool tab_on = !getenv("GGML_MI355X_ROPE_TABLE") || atoi(getenv("GGML_MI355X_ROPE_TABLE")) != 0;
-                    if (!tab_on || rope_m < 1 || rope_m > 64 || rp.n_dims < 2 || rp.n_dims > 256 || (int64_t) rope_m * rp.n_dims > (int64_t) backend_ctx::rope_tab_floats) rope_m = 0;
+                    if (!rope_table_on() || rope_m < 1 || rope_m > 64 || rp.n_dims < 2 || rp.n_dims > 256 || (int64_t) rope_m * rp.n_dims > (int64_t) backend_ctx::rope_tab_floats) rope_m = 0;
                 }
                 if (cast || rope_m > 0) {
                     const tdesc ta = TD(a), tb = TD(b), tn = TD(n);
@@ -2159,7 +2159,7 @@ static int run_node(exec_state & st, int i) {
                         // kqv is read by nothing but that view chain, the product is written where the CONT would have put it and the CONT is done
                         int cont_at = -1;
                         const ggml_tensor * cont = nullptr;
-                        static const bool elide_on = !getenv("GGML_MI355X_ELIDE_CONT") || atoi(getenv("GGML_MI355X_ELIDE_CONT")) != 0;
+                        static const bool elide_on = env_flag("GGML_MI355X_ELIDE_CONT", true);
                         if (elide_on && use_count(st, mm) == 1 && !(mm->flags & GGML_TENSOR_FLAG_OUTPUT)) {
                             const ggml_tensor * cur = mm;
                             for (int k = j + 1; k < std::min(g->n_nodes, j + 6); ++k) {
@@ -2522,7 +2522,7 @@ enum ggml_status graph_compute(backend_ctx * c, ggml_cgraph * g) {
     for (int i = 0; i < g->n_nodes && !has_split; ++i) has_split = g->nodes[i]->op == GGML_OP_MUL_MAT && buffer_is_split(g->nodes[i]->src[0]->buffer);
     // (graphs that launch on several devices' streams: captured only on request — GGML_MI355X_SPLIT_GRAPHS=1 — until that has run on a box
     // with more than one GPU; the fork / join over events is capturable and is exercised on logical devices by tests/test_gpu_split.py)
-    static const bool split_graphs = getenv("GGML_MI355X_SPLIT_GRAPHS") && atoi(getenv("GGML_MI355X_SPLIT_GRAPHS")) != 0;
+    static const bool split_graphs = env_flag("GGML_MI355X_SPLIT_GRAPHS", false);
     const bool want_graph = may_replay && (!has_split || split_graphs);
     if (!want_graph) {
         c->st.eager_graphs++;
@@ -2561,7 +2561,7 @@ enum ggml_status graph_compute(backend_ctx * c, ggml_cgraph * g) {
     // cache (n_kv moves to the next multiple of 256: every 8th step of a -np 32 engine, llama-box/httpserver.hpp:3539-3623): its kernels have
     // all run before, so it is captured at once instead of after an eager run (profiles/r05_np32_ab_early_capture.txt).  Anything else keeps the
     // rule "first sighting eager" — one-off prompt graphs never pay for a capture, and a kernel's first launch never happens inside one.
-    static const bool early_on = !getenv("GGML_MI355X_EARLY_CAPTURE") || atoi(getenv("GGML_MI355X_EARLY_CAPTURE")) != 0;
+    static const bool early_on = env_flag("GGML_MI355X_EARLY_CAPTURE", true);
     const bool early = early_on && cg.seen == 0 && !cg.early_failed && c->last_graph && c->last_graph != &cg && c->last_graph->exec && c->last_graph->n_nodes == g->n_nodes &&
                        c->last_graph->last_use + 1 == c->tick && !has_split && !tp_active(c);
     cached_graph * const prev = early ? c->last_graph : nullptr;

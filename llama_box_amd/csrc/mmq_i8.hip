@@ -545,7 +545,7 @@ int mmq_pick_ksplit(int64_t K, int64_t N, int64_t M, bool skinny, int type) {
     // prompt batches the wide form of mmq_skinny.hip serves run without a K split (its grid fills the chip by token-tile groups)
     if (skinny && mmq_wide_tiles(type, K, &N, 1, M, (K / 256) * (type == GGML_TYPE_Q4_K ? 144 : 176), 1) != 0) return 1;
     const int64_t wgs = ((N + 63) / 64) * ((M + 127) / 128), nblk = K / 256;
-    static const int ks_target = getenv("GGML_MI355X_MMQ_KS_TARGET") ? atoi(getenv("GGML_MI355X_MMQ_KS_TARGET")) : 512;
+    static const int ks_target = env_int("GGML_MI355X_MMQ_KS_TARGET", 512);
     if (M <= 64) return (int) std::max<int64_t>(1, std::min<int64_t>(nblk, ks_target / std::max<int64_t>(1, wgs)));
     // wide batches (prefill micro-batches): only when the output is too small to occupy the chip (wk/wv: 64 workgroups at
     // M = 512), or when a long K leaves exactly one workgroup per CU (ffn_down): measured 36 -> 19 us and 134 -> 117 us
@@ -683,7 +683,7 @@ int launch_mmq_i8_multi(hipStream_t s, int type, int n_mat, const mmq_mat_desc *
     // 128-row panels unless that leaves CUs idle (256 CUs, one 8-wave workgroup each)
     const int64_t wg128 = panels128 * ((M + MI_BM - 1) / MI_BM);
     // continuous-batching decode steps: column tiles of 32 / 64 (always on 64-row panels — the output matrix included)
-    static const int force_bm = getenv("GGML_MI355X_MMQ_BM") ? atoi(getenv("GGML_MI355X_MMQ_BM")) : 0;
+    static const int force_bm = env_int("GGML_MI355X_MMQ_BM", 0);
     const int bm = force_bm ? force_bm : (M <= 32 ? 32 : (M <= 64 ? 64 : 128));
     // 128-row panels (one 8-wave workgroup per CU) when they still fill the chip — except for Q4_K / Q6_K at K < 8192, where 64-row
     // panels (two independent 4-wave workgroups per CU, not behind one barrier) measure 2-3 % ahead on every prompt shape of the 8B

@@ -424,8 +424,8 @@ template <bool WP, int WT = GGML_TYPE_Q8_0> __global__ void __launch_bounds__(Q8
 }
 
 bool mmq_q80_skinny_supported(int type, int64_t K, int64_t N, int64_t M) {
-    static const bool on = !getenv("GGML_MI355X_Q80_SKINNY") || atoi(getenv("GGML_MI355X_Q80_SKINNY")) != 0;
-    static const int max_cols = getenv("GGML_MI355X_Q80_SKINNY_MAX") ? atoi(getenv("GGML_MI355X_Q80_SKINNY_MAX")) : 128;  // (up to 128 columns: four passes of 32 still beat the 128 x 128-tile GEMM's few workgroups — Llama-3-8B Q8_0, 128-token micro-batches: 8.5 k against 5.1 k tok/s)
+    static const bool on = env_flag("GGML_MI355X_Q80_SKINNY", true);
+    static const int max_cols = env_int("GGML_MI355X_Q80_SKINNY_MAX", 128);  // (up to 128 columns: four passes of 32 still beat the 128 x 128-tile GEMM's few workgroups — Llama-3-8B Q8_0, 128-token micro-batches: 8.5 k against 5.1 k tok/s)
     return on && type == GGML_TYPE_Q8_0 && (K % 128) == 0 && N >= 1 && M >= 9 && M <= std::min(max_cols, 128);
 }
 // n matrices (1 .. 3) over the same activations; panels[q] != nullptr for ALL of them or for none (the template form is per launch)

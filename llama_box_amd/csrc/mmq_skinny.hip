@@ -714,10 +714,11 @@ __global__ void __launch_bounds__(TP8_NW * 64, 1) k_mmq_skinny_tp8(const mmq8_ar
 
 // the tile-parallel form serves a launch when every matrix is whole 128-row groups, there is no K split, and the groups alone
 // occupy most of the chip
+// GGML_MI355X_SKINNY_TP: 2 = two waves per tile (Q4_K), 1 = the four-wave form, 0 = the tile-parallel forms off
+static int skinny_tp_mode() { static const int v = env_int("GGML_MI355X_SKINNY_TP", 2); return v; }
 static bool skinny_tp_applies(int type, const mmq8_args & a, int n_cu) {
     if (!(type == GGML_TYPE_Q4_K || type == GGML_TYPE_Q5_K) || a.ksplit != 1) return false;
-    static const bool on = !getenv("GGML_MI355X_SKINNY_TP") || atoi(getenv("GGML_MI355X_SKINNY_TP")) != 0;
-    if (!on) return false;
+    if (skinny_tp_mode() == 0) return false;
     int64_t groups = 0;
     for (int i = 0; i < a.n_mat; ++i) {
         if (a.mat[i].N % 128) return false;
@@ -1029,7 +1030,7 @@ __global__ void __launch_bounds__((NW + NL) * 64, 1) k_mmq_wide(const mmq8_args 
 // of six waves).  Qwen2-7B Q5_K_M (three digit planes: the tiled GEMM spills there) 20.5 -> 25.3 k.  Returns the shape code
 // NW * 16 + TT, or 0.  The caller's activation area must hold whole 128-column groups (columns beyond M are fetched, never stored).
 int mmq_wide_tiles(int type, int64_t K, const int64_t * N, int n_mat, int64_t M, int64_t w_nb1, int ksplit) {
-    static const bool on = !getenv("GGML_MI355X_MMQ_WIDE") || atoi(getenv("GGML_MI355X_MMQ_WIDE")) != 0;
+    static const bool on = env_flag("GGML_MI355X_MMQ_WIDE", true);
     if (!on || !(type == GGML_TYPE_Q4_K || type == GGML_TYPE_Q5_K) || ksplit != 1 || M < 33 || (K % 256) != 0) return 0;
     if (w_nb1 != (K / 256) * (type == GGML_TYPE_Q4_K ? 144 : 176)) return 0;
     int64_t g128 = 0;
@@ -1055,7 +1056,7 @@ template <int QT, int TT, int NW, int NL> static void launch_wide_t(hipStream_t 
     MI_LAUNCH_PROBED((k_mmq_wide<QT, TT, NW, NL>), dim3((unsigned) std::min(n_virtual, skinny_n_cu())), dim3((NW + NL) * 64), lds, s, a);
 }
 void launch_mmq_wide(hipStream_t s, int type, int shape, const mmq8_args & a) {
-    static const int self4 = getenv("GGML_MI355X_MMQ_WIDE_SELF") ? atoi(getenv("GGML_MI355X_MMQ_WIDE_SELF")) : 0;  // experiment: 4 waves x 4 token tiles, no loaders
+    static const int self4 = env_int("GGML_MI355X_MMQ_WIDE_SELF", 0);  // experiment: 4 waves x 4 token tiles, no loaders
     (void) shape;
     if (self4 && type == GGML_TYPE_Q4_K) { launch_wide_t<4, 4, 4, 0>(s, a); return; }
     if (type == GGML_TYPE_Q4_K) launch_wide_t<4, 2, 4, WD_NL>(s, a);
@@ -1103,8 +1104,7 @@ template <int QT> static void launch_skinny_t(hipStream_t s, mmq8_args a) {
             }
             if constexpr (QT == 4) {
                 // two waves per tile (GGML_MI355X_SKINNY_TP=1: the four-wave form)
-                static const bool tp8 = !getenv("GGML_MI355X_SKINNY_TP") || atoi(getenv("GGML_MI355X_SKINNY_TP")) != 1;
-                if (tp8 && (a.K % 512) == 0) {
+                if (skinny_tp_mode() != 1 && (a.K % 512) == 0) {
                     static std::atomic<uint32_t> lds_raised_tp8{0};
                     (void) ensure_dyn_lds((const void *) k_mmq_skinny_tp8<QT>, (size_t) tp8_lds_bytes<QT>(), lds_raised_tp8);
                     MI_LAUNCH_PROBED((k_mmq_skinny_tp8<QT>), dim3((unsigned) std::min(a.n_panels, n_cu)), dim3(TP8_NW * 64), (size_t) tp8_lds_bytes<QT>(), s, a);

@@ -476,7 +476,7 @@ template <typename T, bool GLU, int PRO> static void launch_stream(hipStream_t s
     const int nblk = a.K / T::BLK;
     const size_t lds = (size_t) nblk * sizeof(typename T::act) + 16 * sizeof(double) + 16;
     const unsigned grid = (unsigned) std::min<int64_t>(256, ((int64_t) a.N + 15) / 16);
-    static const int bal = getenv("GGML_MI355X_BALANCE_TAIL") ? atoi(getenv("GGML_MI355X_BALANCE_TAIL")) : 1;
+    static const int bal = env_int("GGML_MI355X_BALANCE_TAIL", 1);
     mmvq_args a2 = a;
     a2.balance_tail = bal;
     if (g_launch_probe.armed && !g_launch_probe.used) {
@@ -543,7 +543,7 @@ template <typename T> static void launch_type(hipStream_t s, const mmvq_args & a
     // Q8_0 weights (no weight-streaming matrix-core kernel for 2 .. 32 columns: mmq_skinny.hip serves the K-quants): 16 or 32 columns in ONE pass when their Q8_0
     // blocks fit the LDS (up to 144 KB, on 16-wave workgroups so that a CU still holds 16 waves) — a -np 32 step used to stream every Q8_0 matrix four times
     // (TinyLlama: 55 % of the step in k_mmvq<T_Q80, 8>, profiles/r06_ab_fa_dec64.txt); same dot products per column, same f32 order
-    static const int wide_cols = getenv("GGML_MI355X_Q80_WIDE_COLS") ? atoi(getenv("GGML_MI355X_Q80_WIDE_COLS")) : 1;
+    static const int wide_cols = env_int("GGML_MI355X_Q80_WIDE_COLS", 1);
     int done = 0;
     while (done < a0.ncols) {
         const int left = a0.ncols - done;

@@ -850,7 +850,7 @@ __global__ void __launch_bounds__(256) k_rope_qk_store_vec(const rope_store_args
     }
 }
 bool rope_qk_store_vec_ok(const rope_store_args & a, int n_tokens) {
-    static const bool on = !getenv("GGML_MI355X_ROPE_VEC") || atoi(getenv("GGML_MI355X_ROPE_VEC")) != 0;
+    static const bool on = env_flag("GGML_MI355X_ROPE_VEC", true);
     if (!on || n_tokens < 33 || a.ks > 1 || a.sk[0].part || a.sk[1].part || a.sk[2].part) return false;
     if ((a.p.mode & ~GGML_ROPE_TYPE_NEOX) != 0 || a.p.n_dims != a.head_dim || (a.head_dim % 8) != 0) return false;
     auto al16 = [](const void * p) { return (((uintptr_t) p) & 15) == 0; };

@@ -336,10 +336,10 @@ void launch_qkv(hipStream_t s, const qkv_args & a0, int type_a, int type_b) {
     // waves per workgroup: 8..16, chosen so that the row-pair units spread over ~256 workgroups (Llama-3-8B: 3072 units ->
     // 12 waves x 256 workgroups; with fixed 16-wave workgroups a quarter of the CUs had nothing to do); the norm prologue
     // needs the whole activation row in one batch of 2 blocks per wave
-    static const int force_nw = getenv("GGML_MI355X_QKV_WAVES") ? atoi(getenv("GGML_MI355X_QKV_WAVES")) : 0;
+    static const int force_nw = env_int("GGML_MI355X_QKV_WAVES", 0);
     // K > 4096 (a unit has several trips) on an f16 cache: the pipelined instantiation — the next trip in flight under the current one's dot
     // products, four activation blocks per wave in the prologue, 8 waves (256 registers each: the Q5_K / Q6_K register sets spill at 12)
-    static const bool pipe_on = !getenv("GGML_MI355X_QKV_PIPE") || atoi(getenv("GGML_MI355X_QKV_PIPE")) != 0;
+    static const bool pipe_on = env_flag("GGML_MI355X_QKV_PIPE", true);
     // ... where 16-wave workgroups would leave half the chip without one (a tensor-split rank's 640 row pairs: 40 workgroups -> 80; measured
     // 13.9 -> 11.9 and 15.8 -> 12.9 us per launch, profiles/r04_ab_qkv_pipe.txt); the unsharded 70B launch (5120 row pairs) measures the same either way
     const bool pipe = pipe_on && nblk > 16 && nblk <= 32 && !q8_store && type_a != GGML_TYPE_Q8_0 && (units[0] + units[1] + 15) / 16 < 128;
@@ -384,7 +384,7 @@ void launch_qkv(hipStream_t s, const qkv_args & a0, int type_a, int type_b) {
         else { MI_ERR("launch_qkv: unsupported weight format %d", type_a); abort(); }
         return;
     }
-    static const bool wave_split = !getenv("GGML_MI355X_QKV_WAVE_SPLIT") || atoi(getenv("GGML_MI355X_QKV_WAVE_SPLIT")) != 0;
+    static const bool wave_split = env_flag("GGML_MI355X_QKV_WAVE_SPLIT", true);
     if (wave_split && !q8_store && !pipe) {
         // split by waves: the smallest grid of nw-wave workgroups that holds one unit per wave (at most 256), format A's units on the first waves
         const int total_units = units[0] + units[1];

@@ -173,8 +173,7 @@ int tp_p2p_attach(backend_ctx * c, const void * handles, size_t size) {
     const char * e = getenv("GGML_MI355X_P2P_MAX_BYTES");
     t->p2p_max_cols_bytes = e ? atoi(e) : 8 * 8192 * 4;  // up to eight columns of a 70B residual stream; longer messages prefer RCCL's ring when there is one
     // as with a communicator: replayed graphs containing cross-rank waits are opt-in (a replay that hangs has no fallback; the kernel's spins are bounded)
-    const char * g = getenv("GGML_MI355X_TP_GRAPHS");
-    const bool env_on = g != nullptr && atoi(g) != 0;
+    const bool env_on = env_flag("GGML_MI355X_TP_GRAPHS", false);
     if (!t->comm) c->opt.graphs = c->opt.graphs && env_on;
     MI_INFO("tensor parallel rank %d / %d: one-shot peer-to-peer all-reduce attached (mailbox %.1f MiB per rank%s)", t->rank, t->world, mbox_bytes(t->world) / 1048576.0,
             t->comm ? ", RCCL for longer messages" : ", no RCCL communicator");

@@ -207,7 +207,7 @@ static ip_engine * engine_new(backend_ctx * c, int n_dev, int main_dev) {
     // on most boxes.  The cause was replica_of(): non-split weights were copied with a device-to-device hipMemcpy, which returns before the copy has run,
     // and the early device read half-copied norm weights.  Same box, same binary, five alternating runs each: the copy as it was 8 of 10 wrong, the
     // stream-ordered copy 10 of 10 equal to the one-device logits (profiles/r05_inproc_tp_submit_order.txt).
-    static const bool threads_on = !(getenv("GGML_MI355X_SPLIT_THREADS") && atoi(getenv("GGML_MI355X_SPLIT_THREADS")) == 0);
+    static const bool threads_on = env_flag("GGML_MI355X_SPLIT_THREADS", true);
     if (ok && threads_on) {
         for (int d = 0; d < n_dev; ++d) {
             if (d == main_dev) continue;
@@ -345,7 +345,7 @@ static void * replica_of(ip_engine * E, int d, const ggml_tensor * t) {
     // ON THE DEVICE'S OWN STREAM: a device-to-device hipMemcpy returns before the copy has run (it goes to the null stream, which the devices' non-blocking
     // streams do not wait for) — a device that got going before the others read half-copied norm weights and embeddings in its first graph (the open question
     // of profiles/r05_inproc_tp_submit_order.txt, answered late in round 5).  The main device's memory is read over peer access by a copy kernel.
-    static const bool dbg_null_stream = getenv("GGML_MI355X_DBG_REPLICA_MEMCPY") != nullptr;  // (the A/B of the evidence file: the copy as it was)
+    static const bool dbg_null_stream = env_present("GGML_MI355X_DBG_REPLICA_MEMCPY");  // (the A/B of the evidence file: the copy as it was)
     if (dbg_null_stream) (void) hipMemcpyPeer(p, E->ordinal[d], t->data, E->main->device, n);
     else launch_copy2d(E->ctx[d]->stream, p, n, t->data, n, n, 1);
     const hipError_t e = hipGetLastError();
@@ -1019,13 +1019,6 @@ static ip_plan * build_plan(ip_engine * E, const ggml_cgraph * g) {
 }
 
 // ------------------------------------------------------------------------------------------------ execution
-static bool same_options(const options & a, const options & b) {
-    return a.graphs == b.graphs && a.fusion == b.fusion && a.prologue == b.prologue && a.qkv == b.qkv && a.mmvq_max_cols == b.mmvq_max_cols && a.mmq_min_cols == b.mmq_min_cols &&
-           a.mmq_i8 == b.mmq_i8 && a.mm_merge == b.mm_merge && a.ss_partials == b.ss_partials && a.fa_self_merge == b.fa_self_merge && a.attn_nf == b.attn_nf &&
-           a.softmax_mm == b.softmax_mm && a.skinny_rope == b.skinny_rope && a.skinny_mix == b.skinny_mix && a.mmq_skinny == b.mmq_skinny && a.mmq_bn == b.mmq_bn &&
-           a.bf16_form == b.bf16_form && a.bf16_mmv_max_cols == b.bf16_mmv_max_cols && a.bf16_nt == b.bf16_nt && a.bf16_preround == b.bf16_preround &&
-           a.fa_splits == b.fa_splits && a.fa_wo == b.fa_wo && a.small_uploads == b.small_uploads && a.small_downloads == b.small_downloads && a.timing == b.timing;
-}
 static bool ensure_stage(ip_engine * E, size_t need) {
     if (need <= E->stage_size) return true;
     for (int d = 0; d < E->n_dev; ++d) {
@@ -1067,7 +1060,7 @@ static enum ggml_status launch_device(ip_engine * E, ip_plan * P, int d) {
     HIP_TRY(hipSetDevice(E->ordinal[d]), GGML_STATUS_FAILED);
     // replayed graphs with cross-device waits: on unless GGML_MI355X_SPLIT_GRAPHS=0 (the kernels' spins are bounded: a device that does not show
     // up costs a failed llama_decode, not a hang)
-    static const bool graphs_ok = !getenv("GGML_MI355X_SPLIT_GRAPHS") || atoi(getenv("GGML_MI355X_SPLIT_GRAPHS")) != 0;
+    static const bool graphs_ok = env_flag("GGML_MI355X_SPLIT_GRAPHS", true);
     const bool graphs_was = w->opt.graphs;
     w->opt.graphs = graphs_was && graphs_ok;
     // debugging aid: GGML_MI355X_DBG_SUBMIT_ORDER=asc | desc | mdesc — the devices' graphs are submitted one after the other in that order
@@ -1108,7 +1101,7 @@ static enum ggml_status run_plan(ip_engine * E, ip_plan * P, const ggml_cgraph *
     backend_ctx * c = E->main;
     struct guard { int dev; ~guard() { if (hipSetDevice(dev) != hipSuccess) (void) hipGetLastError(); } } restore{c->device};
     // options follow the main backend (tests and hosts flip graphs / fusion there)
-    if (!same_options(E->opt_seen, c->opt)) {
+    if (!(E->opt_seen == c->opt)) {
         for (int d = 0; d < E->n_dev; ++d) {
             if (d == E->main_dev) continue;
             if (hipSetDevice(E->ordinal[d]) == hipSuccess) (void) hipStreamSynchronize(E->ctx[d]->stream);
@@ -1208,7 +1201,7 @@ static enum ggml_status run_plan(ip_engine * E, ip_plan * P, const ggml_cgraph *
 
 enum ggml_status ip_graph_compute(backend_ctx * c, ggml_cgraph * g, bool * handled) {
     *handled = false;
-    static const bool on = !getenv("GGML_MI355X_SPLIT_TP") || atoi(getenv("GGML_MI355X_SPLIT_TP")) != 0;
+    static const bool on = env_flag("GGML_MI355X_SPLIT_TP", true);
     if (!on || c->capturing) return GGML_STATUS_SUCCESS;
     ip_engine * E = c->ip;
     if (E && (E->dead || E->running)) return GGML_STATUS_SUCCESS;
