@@ -123,6 +123,8 @@ _SIGS = {
     "ggml_scale": (TP, [_P, TP, _F]), "ggml_scale_bias": (TP, [_P, TP, _F, _F]), "ggml_rms_norm": (TP, [_P, TP, _F]),
     "ggml_mul_mat": (TP, [_P, TP, TP]), "ggml_get_rows": (TP, [_P, TP, TP]), "ggml_set_rows": (TP, [_P, TP, TP, TP]),
     "ggml_silu": (TP, [_P, TP]), "ggml_unary": (TP, [_P, TP, _I]), "ggml_swiglu": (TP, [_P, TP]), "ggml_swiglu_split": (TP, [_P, TP, TP]),
+    "ggml_norm": (TP, [_P, TP, _F]), "ggml_gelu": (TP, [_P, TP]), "ggml_gelu_quick": (TP, [_P, TP]), "ggml_gelu_erf": (TP, [_P, TP]),
+    **{f"ggml_{g}{form}": (TP, [_P, TP] + ([TP] if form == "_split" else [])) for g in ("reglu", "geglu", "geglu_erf", "geglu_quick") for form in ("", "_swapped", "_split")},
     "ggml_soft_max": (TP, [_P, TP]), "ggml_soft_max_ext": (TP, [_P, TP, TP, _F, _F]), "ggml_soft_max_add_sinks": (None, [TP, TP]),
     "ggml_rope_ext": (TP, [_P, TP, TP, TP, _I, _I, _I, _F, _F, _F, _F, _F, _F]),
     "ggml_rope_multi": (TP, [_P, TP, TP, TP, _I, C.POINTER(C.c_int), _I, _I, _F, _F, _F, _F, _F, _F]),

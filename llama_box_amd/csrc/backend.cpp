@@ -540,6 +540,7 @@ static void be_free(ggml_backend_t be) {
     if (c->up_ring) HIP_NOTE(hipHostFree(c->up_ring));
     if (c->fa_lists) HIP_NOTE(hipFree(c->fa_lists));
     if (c->rope_tab) HIP_NOTE(hipFree(c->rope_tab));
+    if (c->act_tab) HIP_NOTE(hipFree(c->act_tab));
     if (c->fa_arrive) HIP_NOTE(hipFree(c->fa_arrive));
     if (c->ss_buf) HIP_NOTE(hipFree(c->ss_buf));
     HIP_SOFT(hipStreamDestroy(c->stream));
@@ -952,7 +953,7 @@ static bool op_numbering_matches_host() {
     }
     static const struct { int op; const char * name; } k_expect[] = {
         {GGML_OP_NONE, "NONE"}, {GGML_OP_DUP, "DUP"}, {GGML_OP_ADD, "ADD"}, {GGML_OP_SUB, "SUB"}, {GGML_OP_MUL, "MUL"}, {GGML_OP_DIV, "DIV"},
-        {GGML_OP_ARGMAX, "ARGMAX"}, {GGML_OP_RMS_NORM, "RMS_NORM"}, {GGML_OP_MUL_MAT, "MUL_MAT"}, {GGML_OP_MUL_MAT_ID, "MUL_MAT_ID"}, {GGML_OP_SCALE, "SCALE"},
+        {GGML_OP_ARGMAX, "ARGMAX"}, {GGML_OP_NORM, "NORM"}, {GGML_OP_RMS_NORM, "RMS_NORM"}, {GGML_OP_MUL_MAT, "MUL_MAT"}, {GGML_OP_MUL_MAT_ID, "MUL_MAT_ID"}, {GGML_OP_SCALE, "SCALE"},
         {GGML_OP_CPY, "CPY"}, {GGML_OP_CONT, "CONT"}, {GGML_OP_RESHAPE, "RESHAPE"}, {GGML_OP_VIEW, "VIEW"}, {GGML_OP_PERMUTE, "PERMUTE"},
         {GGML_OP_TRANSPOSE, "TRANSPOSE"}, {GGML_OP_GET_ROWS, "GET_ROWS"}, {GGML_OP_SET_ROWS, "SET_ROWS"}, {GGML_OP_SOFT_MAX, "SOFT_MAX"},
         {GGML_OP_ROPE, "ROPE"}, {GGML_OP_FLASH_ATTN_EXT, "FLASH_ATTN_EXT"}, {GGML_OP_UNARY, "UNARY"}, {GGML_OP_GLU, "GLU"},

@@ -176,6 +176,7 @@ struct backend_ctx {
     static constexpr int fa_arrive_slots = 16384;
     float * rope_tab = nullptr;   // (cos, sin) per (token, rotation pair) of a small batch: written once per graph run, read by every layer's QKV epilogue
     static constexpr int rope_tab_floats = 4096 * 256;  // (cos, sin) of up to 4096 tokens x 128 pairs (round 4: prompt micro-batches use the table too)
+    uint16_t * act_tab = nullptr;  // T_gelu[65536] then T_quick[65536], f16 bits: ggml-cpu's GELU / GELU_QUICK tables, built on the host and uploaded before the first graph that needs them (graph.cpp: ensure_act_tables)
     int * fa_lists = nullptr;
     size_t fa_lists_bytes = 0;
     // per-class kernel timing (bench)

@@ -241,6 +241,10 @@ static bool mm_id_ok(const ggml_tensor * op) {
 // the 3-D split SwiGLU of an expert FFN ([n_ff, n_used, n_tokens]): rows one row stride apart through every dimension, so the row index is flat
 static bool glu_rows_dense(const ggml_tensor * t) { return t->nb[2] == t->nb[1] * (size_t) t->ne[1] && t->nb[3] == t->nb[2] * (size_t) t->ne[2]; }
 
+// the ops of ops_act.hip: the three GELUs of UNARY and the gated units other than SwiGLU
+static bool is_gelu_op(int u) { return u == GGML_UNARY_OP_GELU || u == GGML_UNARY_OP_GELU_QUICK || u == GGML_UNARY_OP_GELU_ERF; }
+static bool is_act_glu_op(int o) { return o == GGML_GLU_OP_REGLU || o == GGML_GLU_OP_GEGLU || o == GGML_GLU_OP_GEGLU_QUICK || o == GGML_GLU_OP_GEGLU_ERF; }
+
 bool supports_op(const ggml_tensor * op) {
     const ggml_tensor * a = op->src[0];
     const ggml_tensor * b = op->src[1];
@@ -279,16 +283,16 @@ bool supports_op(const ggml_tensor * op) {
             return a->type == GGML_TYPE_F32 && b->type == GGML_TYPE_F32 && op->type == GGML_TYPE_F32;
         case GGML_OP_SCALE:
             return is_f32_contig(a) && is_f32_contig(op);
-        case GGML_OP_RMS_NORM:
+        case GGML_OP_NORM: case GGML_OP_RMS_NORM:
             return a->type == GGML_TYPE_F32 && a->nb[0] == 4 && op->nb[0] == 4;
         case GGML_OP_UNARY: {
             const int u = op->op_params[0];
             const bool ok = u == GGML_UNARY_OP_SILU || u == GGML_UNARY_OP_RELU || u == GGML_UNARY_OP_NEG || u == GGML_UNARY_OP_EXP ||
-                            u == GGML_UNARY_OP_TANH || u == GGML_UNARY_OP_SIGMOID;
+                            u == GGML_UNARY_OP_TANH || u == GGML_UNARY_OP_SIGMOID || is_gelu_op(u);
             return ok && is_f32_contig(a) && is_f32_contig(op);
         }
-        case GGML_OP_GLU:
-            return op->op_params[0] == GGML_GLU_OP_SWIGLU && a->type == GGML_TYPE_F32 && a->nb[0] == 4 && (!b || (b->type == GGML_TYPE_F32 && b->nb[0] == 4)) &&
+        case GGML_OP_GLU:  // (SWIGLU_OAI: refused)
+            return (op->op_params[0] == GGML_GLU_OP_SWIGLU || is_act_glu_op(op->op_params[0])) && a->type == GGML_TYPE_F32 && a->nb[0] == 4 && (!b || (b->type == GGML_TYPE_F32 && b->nb[0] == 4)) &&
                    ((a->ne[2] == 1 && a->ne[3] == 1) || (b && glu_rows_dense(a) && glu_rows_dense(b) && glu_rows_dense(op))) && op->nb[0] == 4;
         case GGML_OP_CPY: case GGML_OP_DUP: case GGML_OP_CONT: {
             const int st = a->type, dt = op->type;
@@ -412,6 +416,56 @@ static ws_plan plan_ws(backend_ctx * c, const ggml_cgraph * g) {
     }
     p.act_bytes = (p.act_bytes + 255) & ~(size_t) 255;
     return p;
+}
+
+// ------------------------------------------------------------------------------------------------ the GELU tables
+// ggml-cpu looks GELU and GELU_QUICK up in two tables of 65 536 f16 results, indexed by the f16 rounding of the argument, which it fills at start-up with the
+// process's own tanhf / expf.  The same loops with the same C library in the same process give the same tables by construction, where a device
+// evaluation with another tanhf would not (1 + tanhf(.) cancels for negative arguments: the f32 result is whole f16 steps off the exact value in places, in a
+// pattern that belongs to the libm).  Each expression is evaluated left to right in f32, uncontracted (this file is compiled with -ffp-contract=off).
+static uint16_t host_f2h(float f) {
+    const _Float16 h = (_Float16) f;  // round to nearest even
+    uint16_t u;
+    memcpy(&u, &h, 2);
+    return u;
+}
+static const uint16_t * act_tables_host() {
+    static const std::vector<uint16_t> tab = [] {
+        std::vector<uint16_t> t(2 * 65536);
+        for (uint32_t i = 0; i < 65536; ++i) {
+            const uint16_t u = (uint16_t) i;
+            _Float16 hh;
+            memcpy(&hh, &u, 2);
+            const volatile float h = (float) hh;  // (volatile: no constant folding of the libm calls)
+            const float x = h;
+            t[i] = host_f2h(0.5f * x * (1.0f + tanhf(0.79788456080286535588f * x * (1.0f + 0.044715f * x * x))));
+            t[65536 + i] = host_f2h(x * (1.0f / (1.0f + expf(-1.702f * x))));
+        }
+        return t;
+    }();
+    return tab.data();
+}
+// once per backend instance, in front of the walk of the first graph that holds a GELU, GELU_QUICK, GEGLU or GEGLU_QUICK node — never inside a capture (the
+// caller is graph_compute, before any); a captured graph then carries the table's address, which lives as long as the backend
+static bool ensure_act_tables(backend_ctx * c, const ggml_cgraph * g) {
+    if (c->act_tab) return true;
+    bool need = false;
+    for (int i = 0; i < g->n_nodes && !need; ++i) {
+        const ggml_tensor * n = g->nodes[i];
+        need = (n->op == GGML_OP_UNARY && (n->op_params[0] == GGML_UNARY_OP_GELU || n->op_params[0] == GGML_UNARY_OP_GELU_QUICK)) ||
+               (n->op == GGML_OP_GLU && (n->op_params[0] == GGML_GLU_OP_GEGLU || n->op_params[0] == GGML_GLU_OP_GEGLU_QUICK));
+    }
+    if (!need) return true;
+    const size_t bytes = 2 * 65536 * sizeof(uint16_t);
+    uint16_t * dev = nullptr;
+    if (hipMalloc((void **) &dev, bytes) != hipSuccess || hipMemcpy(dev, act_tables_host(), bytes, hipMemcpyHostToDevice) != hipSuccess) {
+        (void) hipGetLastError();
+        if (dev) HIP_NOTE(hipFree(dev));
+        MI_ERR("failed to place the GELU tables (%zu bytes) on device %d", bytes, c->device);
+        return false;
+    }
+    c->act_tab = dev;
+    return true;
 }
 
 // ------------------------------------------------------------------------------------------------ attention-mask content hints
@@ -870,6 +924,40 @@ static bool can_defer_norm(const exec_state & st, int i, const ggml_tensor * n, 
         if (!is_view_op(t) && ranges_overlap(t, x)) return false;
     }
     return true;
+}
+
+// NORM n (node i) -> MUL(n, w) [-> ADD(., b)]: llama.cpp's build_norm with LLM_NORM.  k_norm applies the row weight and the bias itself and writes the last
+// node's tensor.  w / b may be on either side of their node.  The guards are those of RMS_NORM -> MUL: the absorbed result has one reader and is no output, the
+// row vector is f32, contiguous, ne0 values and nothing more, the shape is kept.  One more, because the launch reads x while it writes a LATER node's memory,
+// which the host allocator may have cut out of x's recycled block: that memory is x itself (the in-place form, which k_norm allows) or apart from it.
+struct norm_affine {
+    const ggml_tensor * w = nullptr;
+    const ggml_tensor * b = nullptr;
+    const ggml_tensor * out = nullptr;  // the tensor the launch writes: n, the MUL or the ADD
+    int absorbed = 0;                   // nodes behind n that the launch stands for: 0, 1 or 2
+};
+static norm_affine find_norm_affine(const exec_state & st, int i) {
+    const ggml_cgraph * g = st.g;
+    const ggml_tensor * n = g->nodes[i];
+    const ggml_tensor * x = n->src[0];
+    norm_affine f;
+    f.out = n;
+    auto row_vector = [&](const ggml_tensor * v) { return v && v->type == GGML_TYPE_F32 && ggml_abi_is_contiguous(v) && v->ne[0] == n->ne[0] && ggml_abi_nelements(v) == v->ne[0]; };
+    auto dst_ok = [&](const ggml_tensor * d) {
+        return d->type == GGML_TYPE_F32 && d->nb[0] == 4 && same_shape(d, n) &&
+               (!ranges_overlap(d, x) || (d->data == x->data && d->nb[1] == x->nb[1] && d->nb[2] == x->nb[2] && d->nb[3] == x->nb[3]));
+    };
+    const ggml_tensor * cur = n;
+    for (int k = 1; k <= 2 && i + k < g->n_nodes; ++k) {
+        const ggml_tensor * t = g->nodes[i + k];
+        if (t->op != (k == 1 ? GGML_OP_MUL : GGML_OP_ADD) || st.done[i + k] || !single_use(st, cur) || !dst_ok(t)) break;
+        const ggml_tensor * v = t->src[0] == cur ? t->src[1] : (t->src[1] == cur ? t->src[0] : nullptr);
+        if (!row_vector(v)) break;
+        (k == 1 ? f.w : f.b) = v;
+        f.out = cur = t;
+        f.absorbed = k;
+    }
+    return f;
 }
 
 // ------------------------------------------------------------------------------------------------ fused Q/K/V
@@ -1755,6 +1843,16 @@ static int run_node(exec_state & st, int i) {
         case GGML_OP_NONE: case GGML_OP_VIEW: case GGML_OP_RESHAPE: case GGML_OP_PERMUTE: case GGML_OP_TRANSPOSE:
             return 1;
 
+        case GGML_OP_NORM: {
+            // NORM -> MUL(norm, w) [-> ADD(., b)]: one kernel writing the last node's output
+            const norm_affine f = fuse ? find_norm_affine(st, i) : norm_affine{nullptr, nullptr, n, 0};
+            timed_scope ts(c, f.absorbed ? "norm_affine" : "norm", (double) ggml_abi_nbytes(a) * 2);
+            launch_norm(s, TD(a), TD(f.out), ggml_abi_op_param_f32(n, 0), f.w ? (const float *) f.w->data : nullptr, f.b ? (const float *) f.b->data : nullptr);
+            c->st.kernel_launches++;
+            c->st.fused_nodes += f.absorbed;
+            return 1 + f.absorbed;
+        }
+
         case GGML_OP_RMS_NORM: {
             // RMS_NORM -> MUL(norm, w): one kernel writing the MUL's output
             ggml_tensor * m = next(1);
@@ -2014,12 +2112,17 @@ static int run_node(exec_state & st, int i) {
             c->st.kernel_launches++;
             return 1;
         case GGML_OP_UNARY:
+            if (is_gelu_op(n->op_params[0])) {
+                timed_scope ts(c, "gelu", (double) ggml_abi_nbytes(n) * 2);
+                if (!launch_gelu(s, n->op_params[0], TD(a), TD(n), c->act_tab)) return -1;
+            } else
             launch_unary(s, n->op_params[0], TD(a), TD(n));
             c->st.kernel_launches++;
             return 1;
         case GGML_OP_GLU: {
             const tdesc bd = b ? TD(b) : TD(a);
-            if (fuse && c->opt.prologue && ggml_abi_nrows(n) > 1 && (a->nb[1] % 16) == 0 && (!b || (b->nb[1] % 16) == 0) && !(((uintptr_t) a->data) & 15) &&
+            const bool swiglu = n->op_params[0] == GGML_GLU_OP_SWIGLU;  // (the two fused producers and launch_swiglu are SwiGLU's alone)
+            if (swiglu && fuse && c->opt.prologue && ggml_abi_nrows(n) > 1 && (a->nb[1] % 16) == 0 && (!b || (b->nb[1] % 16) == 0) && !(((uintptr_t) a->data) & 15) &&
                 (!b || !(((uintptr_t) b->data) & 15)) && (b || ((n->ne[0] * 4) % 16) == 0) && quant_consumers_only(st, i, n)) {
                 timed_scope ts(c, "swiglu_quantize", (double) ggml_abi_nbytes(n) * 2);
                 launch_swiglu_quantize(s, TD(a), b ? &bd : nullptr, n->ne[0], n->op_params[1], (char *) c->ws + st.act_off);
@@ -2028,12 +2131,18 @@ static int run_node(exec_state & st, int i) {
                 c->st.fused_nodes++;
                 return 1;
             }
-            if (q80_producers_on() && fuse && c->opt.prologue && ggml_abi_nrows(n) >= 9 && swiglu_q80_panel_ok(TD(a), b ? &bd : nullptr, n->ne[0], n->op_params[1]) && q80_panel_consumers_only(st, i, n)) {
+            if (swiglu && q80_producers_on() && fuse && c->opt.prologue && ggml_abi_nrows(n) >= 9 && swiglu_q80_panel_ok(TD(a), b ? &bd : nullptr, n->ne[0], n->op_params[1]) && q80_panel_consumers_only(st, i, n)) {
                 timed_scope ts(c, "swiglu_quantize_q8_0", (double) ggml_abi_nbytes(n) * 2);
                 launch_swiglu_q80_panel(s, TD(a), b ? &bd : nullptr, n->ne[0], n->op_params[1], (char *) c->ws + st.act_off);
                 mark_q8_cache(st, n, MI_ACT_Q80_PANEL);
                 c->st.kernel_launches++;
                 c->st.fused_nodes++;
+                return 1;
+            }
+            if (!swiglu) {  // REGLU, GEGLU, GEGLU_QUICK, GEGLU_ERF (ops_act.hip): no fused producer yet
+                timed_scope ts(c, "glu_act", (double) ggml_abi_nbytes(n) * 3);
+                if (!launch_glu(s, n->op_params[0], TD(a), b ? &bd : nullptr, TD(n), n->op_params[1], c->act_tab)) return -1;
+                c->st.kernel_launches++;
                 return 1;
             }
             timed_scope ts(c, "swiglu", (double) ggml_abi_nbytes(n) * 3);
@@ -2518,6 +2627,7 @@ enum ggml_status graph_compute(backend_ctx * c, ggml_cgraph * g) {
     }
     const ws_plan wp = plan_ws(c, g);
     if (!ensure_ws(c, wp.act_bytes + wp.aux_bytes + 256)) return GGML_STATUS_ALLOC_FAILED;
+    if (!ensure_act_tables(c, g)) return GGML_STATUS_ALLOC_FAILED;
     bool has_split = false;  // multi-device launches + peer copies: executed eagerly (capture across devices is left for a box that has them)
     for (int i = 0; i < g->n_nodes && !has_split; ++i) has_split = g->nodes[i]->op == GGML_OP_MUL_MAT && buffer_is_split(g->nodes[i]->src[0]->buffer);
     // (graphs that launch on several devices' streams: captured only on request — GGML_MI355X_SPLIT_GRAPHS=1 — until that has run on a box

@@ -292,6 +292,12 @@ void launch_rebase_row_index(hipStream_t s, int64_t * dst, const int64_t * src, 
 // live in peer devices' memory: read over xGMI by the main device's kernel)
 struct reduce_parts { const float * part[GGML_MI355X_MAX_DEVICES]; int n; };
 void launch_reduce_parts(hipStream_t s, const reduce_parts & p, const float * add, float * dst, int64_t n);
+// ---- ops_act.hip: LayerNorm, the GELU family, the gated units other than SwiGLU
+// NORM with the optional `* w` and `+ b` of the MUL / ADD nodes behind it (rows of ne0 contiguous f32 each, or nullptr); dst may be src
+void launch_norm(hipStream_t s, const tdesc & src, const tdesc & dst, float eps, const float * mul_w, const float * add_b);
+// act_tab: the two f16 tables of 65 536 entries ggml-cpu looks GELU and GELU_QUICK up in, T_gelu then T_quick (graph.cpp: ensure_act_tables); false = not launched
+bool launch_gelu(hipStream_t s, int unary_op, const tdesc & src, const tdesc & dst, const uint16_t * act_tab);  // GELU, GELU_QUICK, GELU_ERF over contiguous f32
+bool launch_glu(hipStream_t s, int glu_op, const tdesc & a, const tdesc * b, const tdesc & d, int swapped, const uint16_t * act_tab);  // REGLU, GEGLU, GEGLU_QUICK, GEGLU_ERF; operands as launch_swiglu's
 
 
 struct rope_params {
@@ -414,6 +420,7 @@ void tu_touch_mmq_i8(hipStream_t s);
 void tu_touch_mmq_skinny(hipStream_t s);
 void tu_touch_mmq_q80(hipStream_t s);
 void tu_touch_ops(hipStream_t s);
+void tu_touch_ops_act(hipStream_t s);
 void tu_touch_fattn(hipStream_t s);
 void tu_touch_fattn_mma(hipStream_t s);
 void tu_touch_tp_p2p(hipStream_t s);
@@ -435,6 +442,7 @@ inline void preload_kernel_files(hipStream_t s) {
     tu_touch_mmq_skinny(s);
     tu_touch_mmq_q80(s);
     tu_touch_ops(s);
+    tu_touch_ops_act(s);
     tu_touch_fattn(s);
     tu_touch_fattn_mma(s);
     tu_touch_tp_p2p(s);

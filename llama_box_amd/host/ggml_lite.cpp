@@ -349,6 +349,14 @@ struct ggml_tensor * ggml_rms_norm(struct ggml_context * ctx, struct ggml_tensor
     return r;
 }
 
+struct ggml_tensor * ggml_norm(struct ggml_context * ctx, struct ggml_tensor * a, float eps) {
+    ggml_tensor * r = dup_tensor(ctx, a);
+    set_f32(r, 0, eps);
+    r->op = GGML_OP_NORM;
+    r->src[0] = a;
+    return r;
+}
+
 struct ggml_tensor * ggml_mul_mat(struct ggml_context * ctx, struct ggml_tensor * a, struct ggml_tensor * b) {
     LITE_ASSERT(a->ne[0] == b->ne[0] && b->ne[2] % a->ne[2] == 0 && b->ne[3] % a->ne[3] == 0);
     LITE_ASSERT(a->nb[0] <= a->nb[1]);  // !ggml_is_transposed(a)
@@ -389,6 +397,9 @@ struct ggml_tensor * ggml_unary(struct ggml_context * ctx, struct ggml_tensor * 
     return r;
 }
 struct ggml_tensor * ggml_silu(struct ggml_context * ctx, struct ggml_tensor * a) { return ggml_unary(ctx, a, GGML_UNARY_OP_SILU); }
+struct ggml_tensor * ggml_gelu(struct ggml_context * ctx, struct ggml_tensor * a) { return ggml_unary(ctx, a, GGML_UNARY_OP_GELU); }
+struct ggml_tensor * ggml_gelu_quick(struct ggml_context * ctx, struct ggml_tensor * a) { return ggml_unary(ctx, a, GGML_UNARY_OP_GELU_QUICK); }
+struct ggml_tensor * ggml_gelu_erf(struct ggml_context * ctx, struct ggml_tensor * a) { return ggml_unary(ctx, a, GGML_UNARY_OP_GELU_ERF); }
 
 static ggml_tensor * glu_impl(ggml_context * ctx, ggml_tensor * a, ggml_tensor * b, ggml_glu_op op, bool swapped) {
     int64_t ne[4] = {a->ne[0], a->ne[1], a->ne[2], a->ne[3]};
@@ -408,6 +419,16 @@ static ggml_tensor * glu_impl(ggml_context * ctx, ggml_tensor * a, ggml_tensor *
 }
 struct ggml_tensor * ggml_swiglu(struct ggml_context * ctx, struct ggml_tensor * a) { return glu_impl(ctx, a, nullptr, GGML_GLU_OP_SWIGLU, false); }
 struct ggml_tensor * ggml_swiglu_split(struct ggml_context * ctx, struct ggml_tensor * a, struct ggml_tensor * b) { return glu_impl(ctx, a, b, GGML_GLU_OP_SWIGLU, false); }
+// the other gated units: one tensor (halves of a row; _swapped: the gate comes first) or two (_split)
+#define LITE_GLU(name, OP) \
+    struct ggml_tensor * ggml_##name(struct ggml_context * ctx, struct ggml_tensor * a) { return glu_impl(ctx, a, nullptr, OP, false); } \
+    struct ggml_tensor * ggml_##name##_swapped(struct ggml_context * ctx, struct ggml_tensor * a) { return glu_impl(ctx, a, nullptr, OP, true); } \
+    struct ggml_tensor * ggml_##name##_split(struct ggml_context * ctx, struct ggml_tensor * a, struct ggml_tensor * b) { return glu_impl(ctx, a, b, OP, false); }
+LITE_GLU(reglu, GGML_GLU_OP_REGLU)
+LITE_GLU(geglu, GGML_GLU_OP_GEGLU)
+LITE_GLU(geglu_erf, GGML_GLU_OP_GEGLU_ERF)
+LITE_GLU(geglu_quick, GGML_GLU_OP_GEGLU_QUICK)
+#undef LITE_GLU
 
 struct ggml_tensor * ggml_soft_max_ext(struct ggml_context * ctx, struct ggml_tensor * a, struct ggml_tensor * mask, float scale, float max_bias) {
     LITE_ASSERT(ggml_is_contiguous(a));

@@ -78,6 +78,7 @@ struct ggml_tensor * ggml_div(struct ggml_context * ctx, struct ggml_tensor * a,
 struct ggml_tensor * ggml_scale(struct ggml_context * ctx, struct ggml_tensor * a, float s);
 struct ggml_tensor * ggml_scale_bias(struct ggml_context * ctx, struct ggml_tensor * a, float s, float b);
 struct ggml_tensor * ggml_rms_norm(struct ggml_context * ctx, struct ggml_tensor * a, float eps);
+struct ggml_tensor * ggml_norm(struct ggml_context * ctx, struct ggml_tensor * a, float eps);
 struct ggml_tensor * ggml_mul_mat(struct ggml_context * ctx, struct ggml_tensor * a, struct ggml_tensor * b);
 void ggml_mul_mat_set_prec(struct ggml_tensor * a, enum ggml_prec prec);
 struct ggml_tensor * ggml_get_rows(struct ggml_context * ctx, struct ggml_tensor * a, struct ggml_tensor * b);
@@ -86,6 +87,22 @@ struct ggml_tensor * ggml_silu(struct ggml_context * ctx, struct ggml_tensor * a
 struct ggml_tensor * ggml_unary(struct ggml_context * ctx, struct ggml_tensor * a, enum ggml_unary_op op);
 struct ggml_tensor * ggml_swiglu(struct ggml_context * ctx, struct ggml_tensor * a);
 struct ggml_tensor * ggml_swiglu_split(struct ggml_context * ctx, struct ggml_tensor * a, struct ggml_tensor * b);
+struct ggml_tensor * ggml_gelu(struct ggml_context * ctx, struct ggml_tensor * a);
+struct ggml_tensor * ggml_gelu_quick(struct ggml_context * ctx, struct ggml_tensor * a);
+struct ggml_tensor * ggml_gelu_erf(struct ggml_context * ctx, struct ggml_tensor * a);
+/* REGLU / GEGLU / GEGLU_ERF / GEGLU_QUICK: act(x) * g over the halves of a row (x first; _swapped: g first) or over two tensors (_split: a is x, b is g) */
+struct ggml_tensor * ggml_reglu(struct ggml_context * ctx, struct ggml_tensor * a);
+struct ggml_tensor * ggml_reglu_swapped(struct ggml_context * ctx, struct ggml_tensor * a);
+struct ggml_tensor * ggml_reglu_split(struct ggml_context * ctx, struct ggml_tensor * a, struct ggml_tensor * b);
+struct ggml_tensor * ggml_geglu(struct ggml_context * ctx, struct ggml_tensor * a);
+struct ggml_tensor * ggml_geglu_swapped(struct ggml_context * ctx, struct ggml_tensor * a);
+struct ggml_tensor * ggml_geglu_split(struct ggml_context * ctx, struct ggml_tensor * a, struct ggml_tensor * b);
+struct ggml_tensor * ggml_geglu_erf(struct ggml_context * ctx, struct ggml_tensor * a);
+struct ggml_tensor * ggml_geglu_erf_swapped(struct ggml_context * ctx, struct ggml_tensor * a);
+struct ggml_tensor * ggml_geglu_erf_split(struct ggml_context * ctx, struct ggml_tensor * a, struct ggml_tensor * b);
+struct ggml_tensor * ggml_geglu_quick(struct ggml_context * ctx, struct ggml_tensor * a);
+struct ggml_tensor * ggml_geglu_quick_swapped(struct ggml_context * ctx, struct ggml_tensor * a);
+struct ggml_tensor * ggml_geglu_quick_split(struct ggml_context * ctx, struct ggml_tensor * a, struct ggml_tensor * b);
 struct ggml_tensor * ggml_soft_max(struct ggml_context * ctx, struct ggml_tensor * a);
 struct ggml_tensor * ggml_soft_max_ext(struct ggml_context * ctx, struct ggml_tensor * a, struct ggml_tensor * mask, float scale, float max_bias);
 void ggml_soft_max_add_sinks(struct ggml_tensor * a, struct ggml_tensor * sinks);
