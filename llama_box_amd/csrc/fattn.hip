@@ -9,7 +9,7 @@
 // Decode-first layout (batch-1 / small-batch attention is bound by the KV bytes, 131 072 B x n_past per token for
 // Llama-3-8B): one workgroup per (KV split, KV head, query token) serves ALL G query heads that share the KV head,
 // so K/V are read once per group.  A K/V row (D halves) is covered by D/8 lanes with 16-byte loads: a wave64 load
-// instruction moves 8 (D=64) or 4 (D=128) whole rows = 1 KiB, fully coalesced.  Scores are finished with a
+// instruction moves 8 (D=64), 4 (D=128) or 2 (D=256: Gemma) whole rows = 1 KiB, fully coalesced.  Scores are finished with a
 // sub-wave butterfly; there is no LDS traffic in the KV loop.  Partial (m, l, acc) triples are merged across
 // sub-rows (shuffles), waves (LDS) and splits (second tiny kernel).
 #include <algorithm>
@@ -60,6 +60,17 @@ __device__ __forceinline__ float xrow_allsum(const float x) {
     b = y;
     asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(a), "+v"(b));
     return a + b;
+}
+
+// (x.lo+x.hi | y.lo+y.hi): lanes 0-31 get the two-half total of x, lanes 32-63 that of y
+__device__ __forceinline__ float swap32_pairsum(float x, float y) {
+    asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(x), "+v"(y));
+    return x + y;
+}
+// rows (0,1,2,3) get (c.r0+c.r1, d.r0+d.r1, c.r2+c.r3, d.r2+d.r3)
+__device__ __forceinline__ float swap16_pairsum(float c, float d) {
+    asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(c), "+v"(d));
+    return c + d;
 }
 
 template <int D, int G>
@@ -137,7 +148,10 @@ __global__ void __launch_bounds__(256) k_fattn_split(const tdesc q, const tdesc 
 #pragma unroll
                 for (int i = 0; i < 8; ++i) t = fmaf(kf[i], qr[g][i], t);
                 // finish the D-wide dot inside the LPR lanes of the row on the DPP path
-                if constexpr (LPR == 16) {
+                if constexpr (LPR == 32) {  // head size 256: a row is two DPP rows — their sums meet in one half-row swap
+                    t = row16_sum(t);
+                    t = swap16_pairsum(t, t);
+                } else if constexpr (LPR == 16) {
                     t = row16_sum(t);
                 } else {
                     t += dpp_f32<MI_DPP_QUAD_XOR1>(t);
@@ -186,12 +200,13 @@ __global__ void __launch_bounds__(256) k_fattn_split(const tdesc q, const tdesc 
     for (int g = 0; g < G; ++g) {
         float lt = l[g];
         if constexpr (LPR == 8) lt += dpp_f32<MI_DPP_ROR8>(lt);
-        lt = xrow_allsum(lt);
+        // (head size 256: two sub-rows — lanes l and l ^ 32 hold the same dims of the two rows, lanes l and l ^ 16 DIFFERENT dims of one row: only the halves add)
+        lt = LPR == 32 ? swap32_pairsum(lt, lt) : xrow_allsum(lt);
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
             float a = acc[g][i];
             if constexpr (LPR == 8) a += dpp_f32<MI_DPP_ROR8>(a);
-            acc[g][i] = xrow_allsum(a);
+            acc[g][i] = LPR == 32 ? swap32_pairsum(a, a) : xrow_allsum(a);
         }
         l[g] = lt;
     }
@@ -251,16 +266,6 @@ __global__ void __launch_bounds__(256) k_fattn_split(const tdesc q, const tdesc 
 typedef _Float16 fa_half2 __attribute__((ext_vector_type(2)));
 
 __device__ __forceinline__ float fa_exp2(const float x) { return __builtin_amdgcn_exp2f(x); }
-// (x.lo+x.hi | y.lo+y.hi): lanes 0-31 get the two-half total of x, lanes 32-63 that of y
-__device__ __forceinline__ float swap32_pairsum(float x, float y) {
-    asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(x), "+v"(y));
-    return x + y;
-}
-// rows (0,1,2,3) get (c.r0+c.r1, d.r0+d.r1, c.r2+c.r3, d.r2+d.r3)
-__device__ __forceinline__ float swap16_pairsum(float c, float d) {
-    asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(c), "+v"(d));
-    return c + d;
-}
 __device__ __forceinline__ float xrow_allmax(const float x) {
     float a = x, b = x;
     asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(a), "+v"(b));
@@ -1130,8 +1135,10 @@ void launch_flash_attn_combine(hipStream_t s, int D, const float * ws, const flo
         hipLaunchKernelGGL((k_fattn_combine<128, true>), dim3((unsigned) (n_head / 2), (unsigned) n_q, (unsigned) n_batch), dim3(256), 0, s, ws, sinks, dst, geo, (q8k_dev *) q8_out);
         return;
     }
-    if (D == 128) hipLaunchKernelGGL((k_fattn_combine<128>), g2, dim3(128), 0, s, ws, sinks, dst, geo);
-    else hipLaunchKernelGGL((k_fattn_combine<64>), g2, dim3(64), 0, s, ws, sinks, dst, geo);
+    if (D == 256) hipLaunchKernelGGL((k_fattn_combine<256>), g2, dim3(256), 0, s, ws, sinks, dst, geo);
+    else if (D == 128) hipLaunchKernelGGL((k_fattn_combine<128>), g2, dim3(128), 0, s, ws, sinks, dst, geo);
+    else if (D == 64) hipLaunchKernelGGL((k_fattn_combine<64>), g2, dim3(64), 0, s, ws, sinks, dst, geo);
+    else { MI_ERR("launch_flash_attn_combine: no combine pass for head_dim %d", D); abort(); }
 }
 
 bool fattn_prefers_lists(const tdesc & q, const tdesc * mask, int mask_sparse) {
@@ -1139,7 +1146,7 @@ bool fattn_prefers_lists(const tdesc & q, const tdesc * mask, int mask_sparse) {
     return on && mask != nullptr && q.ne[1] >= fattn_mma_min_q() && q.ne[1] <= 256 && mask_sparse != 0;
 }
 int fattn_pick_splits(const tdesc & q, const tdesc & k, const tdesc * mask, int mask_sparse) {
-    if (q.ne[1] >= fattn_mma_min_q() && (k.ne[0] == 64 || k.ne[0] == 128) && !fattn_prefers_lists(q, mask, mask_sparse)) return fattn_mma_pick_splits(q, k);  // (soft-capped / ALiBi batches fall back to the generic kernel with this count)
+    if (q.ne[1] >= fattn_mma_min_q() && (k.ne[0] == 64 || k.ne[0] == 128 || k.ne[0] == 256) && !fattn_prefers_lists(q, mask, mask_sparse)) return fattn_mma_pick_splits(q, k);  // (soft-capped / ALiBi batches fall back to the generic kernel with this count)
     const int64_t n_kv = k.ne[1];
     if (q.ne[1] > 1 && (k.ne[0] == 128 || (k.ne[0] == 64 && k.type == GGML_TYPE_F16 && k.ne[2] > 0 && q.ne[2] % k.ne[2] == 0 && fa_g_ok(q.ne[2] / k.ne[2]))) && q.ne[3] == 1) {
         // a few tokens at head_dim 128 (continuous-batching decode, speculative batches): the tile-list kernel — every split takes a
@@ -1514,6 +1521,7 @@ void launch_flash_attn(hipStream_t s, const tdesc & q, const tdesc & k, const td
     if (D == DD && G == GG) { launch_fa<DD, GG>(s, q, k, v, mk, sinks, dst, geo, ws); return; }
     FA_CASE(64, 1) FA_CASE(64, 2) FA_CASE(64, 3) FA_CASE(64, 4) FA_CASE(64, 5) FA_CASE(64, 6) FA_CASE(64, 7) FA_CASE(64, 8)
     FA_CASE(128, 1) FA_CASE(128, 2) FA_CASE(128, 3) FA_CASE(128, 4) FA_CASE(128, 5) FA_CASE(128, 6) FA_CASE(128, 7) FA_CASE(128, 8)
+    FA_CASE(256, 1) FA_CASE(256, 2) FA_CASE(256, 3) FA_CASE(256, 4) FA_CASE(256, 5) FA_CASE(256, 6) FA_CASE(256, 7) FA_CASE(256, 8)
 #undef FA_CASE
     MI_ERR("launch_flash_attn: unsupported head_dim %d / group %d", D, G);
     abort();

@@ -29,13 +29,16 @@ typedef float float16v __attribute__((ext_vector_type(16)));
 
 struct fam_geom {
     int n_q, n_head, n_kv_head, n_kv, has_mask, n_splits;
-    float scale;
+    float scale;    // (soft-capped forms: scale / softcap)
+    float softcap;  // head size 256 only (fattn_mma_d256)
 };
 
 // NW waves of 32 queries each share one staged K/V tile (NW = 4: 128 queries per workgroup, half the staging work per query)
-template <int D, int NW>
+// (D = 256 — Gemma — is specialised below, k_fattn_mma<256, NW, CAP>: a walk of its own on one wave per SIMD.  CAP, soft-capped scores, exists at that head size only)
+template <int D, int NW, bool CAP = false>
 __global__ void __launch_bounds__(NW * 64, 2) k_fattn_mma(const tdesc q, const tdesc k, const tdesc v, const tdesc mask, const tdesc dst, const fam_geom geo, float * __restrict__ ws,
                                                        const uint8_t * __restrict__ vis) {
+    static_assert(!CAP && (D == 64 || D == 128), "head size 256 and soft-capping: the specialisations below");
     constexpr int BKV = 64;
     constexpr int KS = (D + 8) * 2;    // K tile row stride (bytes): odd multiple of 16 -> conflict-free ds_read_b128
     constexpr int VS = (BKV + 4) * 2;  // V^T tile row stride (bytes): 34 dwords -> conflict-free ds_read_b64 across 32 rows
@@ -303,6 +306,296 @@ __global__ void __launch_bounds__(NW * 64, 2) k_fattn_mma(const tdesc q, const t
         }
     }
 }
+
+// ------------------------------------------------------------------------------------------------ head size 256 (Gemma 1 / 2 / 3)
+// The walk above at D = 256 wants, per lane, 128 output accumulators (O[8]), the query's 16 fragments (64 registers), a score tile (32) and a staged tile (64 at
+// NW = 4, 128 at NW = 2): ~290 / ~350 registers where two waves per SIMD leave 256 (vector and accumulator registers are ONE 512-entry file on gfx950).
+// Choice: ONE wave per SIMD (__launch_bounds__(NW * 64, 1): a four-wave workgroup per CU, or two two-wave ones — 2 x 67 KiB of tiles fit the CU's 160 KiB), the
+// accumulators in the AGPR half of the file (the allocator has to be told: see the loop).  What must be an architectural VGPR — queries, scores, mask words, staged
+// tile, addresses — is 254 .. 256 registers at NW = 2 with 64 of them staging; a whole next tile held in registers (128) cannot fit, so a tile is staged in the two
+// halves of its iteration:
+//    store K(t) -> LDS | request V(t) | barrier | S = K.Q^T, softmax | store V(t) -> LDS | request K(t + 1) | barrier | O += V^T.P^T
+// K(t + 1) flies during P.V and the next tile's decisions, V(t) during K.Q^T and the softmax; only one of the two is in registers at a time (32 of them at NW = 4,
+// 64 at NW = 2).  Still two barriers per tile: the first also says "every wave is done with V^T of the previous tile", the second "... with K of this one".
+// Cost: a SIMD has no second wave to run at the barriers and during the softmax, and a load has half a tile of matrix work (twice as long as a head-size-128
+// tile's) to arrive in, not a whole one.  Not chosen: queries re-read from LDS (64 KiB more of it at NW = 4, 32 KiB at NW = 2 — one workgroup per CU either way, and
+// every K.Q^T step reads two operands from LDS), P.V in two passes over halves of D (every score computed twice: 1.5 x the matrix work), a 32-cell tile (twice the
+// barriers and softmax updates per cell, and the tile states' 64-cell granule no longer the kernel's).
+// CAP (Gemma-2 caps every attention node): s = cap * tanh(s * scale / cap) on the f32 score, before the mask and before the base-2 conversion; geo.scale holds
+// scale / cap.  Tile layouts, operand order, tile states, split records and the arithmetic of the uncapped score are k_fattn_mma's.
+template <int D, int NW, bool CAP>
+__device__ __forceinline__ void fattn_mma_d256(const tdesc & q, const tdesc & k, const tdesc & v, const tdesc & mask, const tdesc & dst, const fam_geom & geo, float * __restrict__ ws,
+                                               const uint8_t * __restrict__ vis, char * smem) {
+    constexpr int BKV = 64;
+    constexpr int KS = (D + 8) * 2, VS = (BKV + 4) * 2, NS = D / 16, ND = D / 32;
+    char * Kt = smem;             // [BKV][D+8] f16
+    char * Vt = smem + BKV * KS;  // [D][BKV+4] f16 (transposed, swizzled)
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int fr = lane & 31, kg = lane >> 5;
+    const int h = blockIdx.y, bat = blockIdx.z / geo.n_splits, split = blockIdx.z % geo.n_splits;
+    const int tiles = (geo.n_kv + BKV - 1) / BKV, tps = (tiles + geo.n_splits - 1) / geo.n_splits;
+    const int kv_begin = split * tps * BKV, kv_end = min(geo.n_kv, kv_begin + tps * BKV);
+    const int kvh = h / (geo.n_head / geo.n_kv_head);
+    const int qi = blockIdx.x * (NW * 32) + wave * 32 + fr;
+    const int qrow = min(qi, geo.n_q - 1);
+    const int64_t kb = bat / (q.ne[3] / k.ne[3]), vb = bat / (q.ne[3] / v.ne[3]);
+    half8 qf[NS];
+    {
+        const float * qp = (const float *) (q.data + (int64_t) qrow * q.nb[1] + (int64_t) h * q.nb[2] + (int64_t) bat * q.nb[3]);
+#pragma unroll
+        for (int s = 0; s < NS; ++s) {
+            const float4 a = *(const float4 *) (qp + 16 * s + 8 * kg), b = *(const float4 *) (qp + 16 * s + 8 * kg + 4);
+            qf[s] = (half8){(_Float16) a.x, (_Float16) a.y, (_Float16) a.z, (_Float16) a.w, (_Float16) b.x, (_Float16) b.y, (_Float16) b.z, (_Float16) b.w};
+        }
+    }
+    const uint16_t * mrow = geo.has_mask ? (const uint16_t *) (mask.data + (int64_t) qrow * mask.nb[1] + (int64_t) (bat % mask.ne[3]) * mask.nb[3]) : nullptr;
+    const char * kbase = k.data + (int64_t) kvh * k.nb[2] + kb * k.nb[3];
+    const char * vbase = v.data + (int64_t) kvh * v.nb[2] + vb * v.nb[3];
+
+    constexpr float LOG2E = 1.4426950408889634f;
+    const float sc2 = geo.scale * LOG2E;
+    // CAP: tanh(x) = 1 - 2 / (e^2x + 1) on v_exp_f32 and v_rcp_f32 (1 ulp each): absolute error <= 2e-7 in the tangent, cap * 2e-7 (1e-5 at Gemma-2's 50) in a score
+    // — a relative 1e-5 in a probability that is rounded to f16 (5e-4) next; e = inf / 0 saturates it to +-1.  (ocml's tanhf is ~40 instructions for each of a lane's
+    // 32 scores per tile: more than the tile's matrix work.)
+    const float x2 = geo.scale * (2.0f * LOG2E), capl2 = geo.softcap * LOG2E;
+    auto cap_tanh = [&](const float s) __attribute__((always_inline)) { return 1.0f - 2.0f * __builtin_amdgcn_rcpf(__builtin_amdgcn_exp2f(s * x2) + 1.0f); };
+    float16v O[ND];
+#pragma unroll
+    for (int dt = 0; dt < ND; ++dt)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) O[dt][r] = 0.0f;
+    const float16v zero = O[0];
+    float m = -INFINITY, l = 0.0f;
+
+    constexpr int T = NW * 64;
+    const int srow = tid / NW, spart = tid % NW;
+    constexpr int CH = D / (8 * NW);
+    constexpr int NBLK = 16 * (D / 8), VB = NBLK / T;
+    static_assert(VB * T == NBLK, "whole V blocks per thread");
+    const int kt_begin = kv_begin / BKV, kt_end = (kv_end + BKV - 1) / BKV;
+    uint8_t * const vt = (uint8_t *) (smem + BKV * KS + D * VS);
+    if (vis) {  // this split's tile states, the NW query tiles packed into a byte (as k_fattn_mma)
+        const int n_qt = (geo.n_q + 31) / 32;
+        const uint8_t * visrow = vis + (int64_t) (blockIdx.x * NW) * tiles;
+        for (int i = kt_begin + tid; i < kt_end; i += T) {
+            uint32_t b = 0;
+#pragma unroll
+            for (int w = 0; w < NW; ++w)
+                if ((int) blockIdx.x * NW + w < n_qt) b |= (uint32_t) (visrow[(int64_t) w * tiles + i] & 3) << (2 * w);
+            vt[i - kt_begin] = (uint8_t) b;
+        }
+        __syncthreads();
+    }
+    auto next_tile = [&](int kt) __attribute__((always_inline)) {
+        if (vis)
+            while (kt < kt_end && __builtin_amdgcn_readfirstlane((int) vt[kt - kt_begin]) == 0) ++kt;
+        return kt;
+    };
+    typedef uint32_t u32x4v __attribute__((ext_vector_type(4)));
+    u32x4v kr[CH];
+    uint4 vr[VB][4];
+    auto load_k = [&](const int kt) __attribute__((always_inline)) {
+        const int pos = min(kt * BKV + srow, geo.n_kv - 1);
+        const u32x4v * kp = (const u32x4v *) (kbase + (int64_t) pos * k.nb[1]) + spart * CH;
+#pragma unroll
+        for (int i = 0; i < CH; ++i) kr[i] = kp[i];
+    };
+    auto store_k = [&]() __attribute__((always_inline)) {
+#pragma unroll
+        for (int i = 0; i < CH; ++i) *(u32x4v *) (Kt + srow * KS + (spart * CH + i) * 16) = kr[i];
+    };
+    auto load_v = [&](const int kt) __attribute__((always_inline)) {  // a thread: VB blocks of 4 KV rows x 8 head dims
+#pragma unroll
+        for (int j = 0; j < VB; ++j) {
+            const int b = tid + j * T, kvq = b / (D / 8), dch = b % (D / 8);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int pos = min(kt * BKV + 4 * kvq + r, geo.n_kv - 1);
+                vr[j][r] = *((const uint4 *) (vbase + (int64_t) pos * v.nb[1]) + dch);
+            }
+        }
+    };
+    auto store_v = [&]() __attribute__((always_inline)) {  // transposed in registers, groups of 4 KV positions XOR-swizzled by the row's 32-dim tile (k_fattn_mma: store_tile)
+#pragma unroll
+        for (int j = 0; j < VB; ++j) {
+            const int b = tid + j * T, kvq = b / (D / 8), dch = b % (D / 8);
+            const uint32_t r0[4] = {vr[j][0].x, vr[j][0].y, vr[j][0].z, vr[j][0].w}, r1[4] = {vr[j][1].x, vr[j][1].y, vr[j][1].z, vr[j][1].w};
+            const uint32_t r2[4] = {vr[j][2].x, vr[j][2].y, vr[j][2].z, vr[j][2].w}, r3[4] = {vr[j][3].x, vr[j][3].y, vr[j][3].z, vr[j][3].w};
+            const int kvs = 8 * (kvq ^ (2 * (dch >> 2)));
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                uint2 lo, hi;
+                lo.x = __builtin_amdgcn_perm(r1[e], r0[e], 0x05040100u);
+                lo.y = __builtin_amdgcn_perm(r3[e], r2[e], 0x05040100u);
+                hi.x = __builtin_amdgcn_perm(r1[e], r0[e], 0x07060302u);
+                hi.y = __builtin_amdgcn_perm(r3[e], r2[e], 0x07060302u);
+                *(uint2 *) (Vt + (8 * dch + 2 * e) * VS + kvs) = lo;
+                *(uint2 *) (Vt + (8 * dch + 2 * e + 1) * VS + kvs) = hi;
+            }
+        }
+    };
+
+    int kt = next_tile(kt_begin);
+    if (kt < kt_end) load_k(kt);
+    while (kt < kt_end) {
+        const int kv0 = kt * BKV;
+        const int mine = !vis ? 1 : (int) __builtin_amdgcn_readfirstlane((vt[kt - kt_begin] >> (2 * wave)) & 3);
+        const bool tail = kv0 + BKV > geo.n_kv;
+        // the accumulators live in the AGPR half of the register file (the matrix instructions read and write them there; only the rare rescale moves them through
+        // VGPRs): said once per tile — left to itself the allocator carried most of O through VGPRs around every branch and spilled what no longer fitted
+#pragma unroll
+        for (int dt = 0; dt < ND; ++dt) asm volatile("" : "+a"(O[dt]));
+        store_k();  // (every wave has passed the second barrier of the previous tile: nobody reads Kt)
+        uint2 mw[2][4] = {};
+        const bool use_mask = geo.has_mask != 0 && mine == 1;  // (wave-uniform)
+        if (use_mask) {  // requested before V: vmcnt retires in order, waiting for these leaves V in flight
+#pragma unroll
+            for (int t = 0; t < 2; ++t)
+#pragma unroll
+                for (int g4 = 0; g4 < 4; ++g4) mw[t][g4] = *(const uint2 *) (mrow + min(kv0 + 32 * t + 8 * g4 + 4 * kg, geo.n_kv - 4));
+        }
+        load_v(kt);
+        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");  // K of this tile is in LDS; every wave is done with V^T of the previous one
+
+        float16v S[2];
+        bool pv = false;  // (wave-uniform) this wave has probabilities to multiply
+        if (mine != 0) {
+#pragma unroll
+            for (int t = 0; t < 2; ++t) {
+                S[t] = zero;
+#pragma unroll
+                for (int s = 0; s < NS; ++s) {
+                    const half8 a = *(const half8 *) (Kt + (32 * t + fr) * KS + (16 * s + 8 * kg) * 2);
+                    S[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, qf[s], S[t], 0, 0, 0);
+                }
+            }
+            float mx = -INFINITY;
+            if (use_mask || tail) {
+#pragma unroll
+                for (int t = 0; t < 2; ++t) {
+#pragma unroll
+                    for (int g4 = 0; g4 < 4; ++g4) {
+                        const int p0 = kv0 + 32 * t + 8 * g4 + 4 * kg;
+                        float mv[4] = {0.f, 0.f, 0.f, 0.f};
+                        if (use_mask) {
+                            mv[0] = h2f((uint16_t) (mw[t][g4].x & 0xFFFF)); mv[1] = h2f((uint16_t) (mw[t][g4].x >> 16));
+                            mv[2] = h2f((uint16_t) (mw[t][g4].y & 0xFFFF)); mv[3] = h2f((uint16_t) (mw[t][g4].y >> 16));
+                        }
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) {
+                            float sv;
+                            if constexpr (CAP) sv = fmaf(cap_tanh(S[t][4 * g4 + e]), capl2, mv[e] * LOG2E);
+                            else sv = fmaf(S[t][4 * g4 + e], sc2, mv[e] * LOG2E);
+                            if (p0 + e >= geo.n_kv) sv = -INFINITY;
+                            S[t][4 * g4 + e] = sv;
+                            mx = fmaxf(mx, sv);
+                        }
+                    }
+                }
+            } else {
+#pragma unroll
+                for (int t = 0; t < 2; ++t)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        float sv;
+                        if constexpr (CAP) sv = cap_tanh(S[t][r]) * capl2;
+                        else sv = S[t][r] * sc2;
+                        S[t][r] = sv;
+                        mx = fmaxf(mx, sv);
+                    }
+            }
+            mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+            const float m_new = fmaxf(m, mx);
+            if (!__all(m_new == -INFINITY)) {  // (else: nothing visible to any query of this wave yet)
+                const float mref = m_new == -INFINITY ? 0.0f : m_new;
+                const float alpha = __builtin_amdgcn_exp2f(m - mref);
+                float rs = 0.0f;
+#pragma unroll
+                for (int t = 0; t < 2; ++t)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        const float p = __builtin_amdgcn_exp2f(S[t][r] - mref);
+                        S[t][r] = p;
+                        rs += p;
+                    }
+                rs += __shfl_xor(rs, 32, 64);
+                l = l * alpha + rs;
+                m = m_new;
+                if (!__all(alpha == 1.0f)) {  // one d-tile at a time through VGPRs and back: 16 registers in flight, not 128
+#pragma unroll
+                    for (int dt = 0; dt < ND; ++dt) {
+                        asm volatile("" : "+a"(O[dt]));  // (still an AGPR value here: the copy into VGPRs is not hoisted to the loop's top)
+                        float16v o = O[dt];
+#pragma unroll
+                        for (int r = 0; r < 16; ++r) o[r] *= alpha;
+                        asm volatile("" : "+a"(o));
+                        O[dt] = o;
+                        __builtin_amdgcn_sched_barrier(0);  // (the scheduler would start all eight at once)
+                    }
+                }
+                pv = true;
+            }
+        }
+        store_v();
+        const int kt_next = next_tile(kt + 1);
+        if (kt_next < kt_end) load_k(kt_next);
+        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");  // V^T of this tile is in LDS; every wave is done with K of it
+        kt = kt_next;
+        if (pv) {
+#pragma unroll
+            for (int t = 0; t < 2; ++t) {
+#pragma unroll
+                for (int s2 = 0; s2 < 2; ++s2) {
+                    half8 pb;
+#pragma unroll
+                    for (int u = 0; u < 8; ++u) pb[u] = (_Float16) S[t][8 * s2 + u];
+                    const int kvg = 8 * t + 4 * s2 + kg;
+#pragma unroll
+                    for (int dt = 0; dt < ND; ++dt) {
+                        const char * vrow = Vt + (32 * dt + fr) * VS;
+                        const half4v a0 = *(const half4v *) (vrow + 8 * (kvg ^ (2 * dt))), a1 = *(const half4v *) (vrow + 8 * ((kvg + 2) ^ (2 * dt)));
+                        const half8 a = (half8){a0[0], a0[1], a0[2], a0[3], a1[0], a1[1], a1[2], a1[3]};
+                        O[dt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, pb, O[dt], 0, 0, 0);
+                    }
+                }
+            }
+        }
+    }
+    if (qi >= geo.n_q) return;
+    if (geo.n_splits == 1) {
+        const float inv = 1.0f / l;
+        float * out = (float *) (dst.data + (int64_t) h * dst.nb[1] + (int64_t) qi * dst.nb[2] + (int64_t) bat * dst.nb[3]);
+#pragma unroll
+        for (int dt = 0; dt < ND; ++dt)
+#pragma unroll
+            for (int g4 = 0; g4 < 4; ++g4) {
+                const int d0 = 32 * dt + 8 * g4 + 4 * kg;
+                *(float4 *) (out + d0) = make_float4(O[dt][4 * g4] * inv, O[dt][4 * g4 + 1] * inv, O[dt][4 * g4 + 2] * inv, O[dt][4 * g4 + 3] * inv);
+            }
+    } else {  // partial record (O relative to m, m, l) in the layout k_fattn_combine reads
+        float * rec = ws + ((((int64_t) bat * geo.n_q + qi) * geo.n_head + h) * geo.n_splits + split) * (D + 2);
+#pragma unroll
+        for (int dt = 0; dt < ND; ++dt)
+#pragma unroll
+            for (int g4 = 0; g4 < 4; ++g4) {
+                const int d0 = 32 * dt + 8 * g4 + 4 * kg;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) rec[d0 + e] = O[dt][4 * g4 + e];
+            }
+        if (kg == 0) {
+            rec[D] = m * (1.0f / LOG2E);  // the combine pass works in the natural-log domain
+            rec[D + 1] = l;
+        }
+    }
+}
+#define FAM_D256(NW, CAP)                                                                                                                                                                  \
+    template <> __global__ void __launch_bounds__(NW * 64, 1) k_fattn_mma<256, NW, CAP>(const tdesc q, const tdesc k, const tdesc v, const tdesc mask, const tdesc dst, const fam_geom geo, \
+                                                                                        float * __restrict__ ws, const uint8_t * __restrict__ vis) {                                     \
+        extern __shared__ __attribute__((aligned(16))) char smem[];                                                                                                                      \
+        fattn_mma_d256<256, NW, CAP>(q, k, v, mask, dst, geo, ws, vis, smem);                                                                                                           \
+    }
+FAM_D256(4, false) FAM_D256(4, true) FAM_D256(2, false) FAM_D256(2, true)
+#undef FAM_D256
 
 // ------------------------------------------------------------------------------------------------ the NON-FLASH chain of a prompt micro-batch
 // llama-box runs with -fa off unless asked (engine_param.hpp:772-779): a prompt chunk then reaches the backend as
@@ -616,10 +909,20 @@ int fattn_mma_min_q() {
 }
 bool flash_attn_mma_applies(const tdesc & q, const tdesc & k, const tdesc * mask, const float * sinks, const tdesc & dst, const fattn_params & p) {
     const int D = (int) k.ne[0];
-    if (q.ne[1] < fattn_mma_min_q() || sinks != nullptr || p.max_bias != 0.0f || p.logit_softcap != 0.0f || (D != 64 && D != 128)) return false;
+    if (q.ne[1] < fattn_mma_min_q() || sinks != nullptr || p.max_bias != 0.0f || (D != 64 && D != 128 && D != 256)) return false;
+    if (p.logit_softcap != 0.0f && D != 256) return false;  // (soft-capped batches at 64 / 128 keep the generic kernel; at 256 — Gemma-2 caps every node — the CAP forms)
     if ((k.ne[1] % 4) != 0 || (q.nb[1] % 16) || (q.nb[2] % 16) || (((uintptr_t) q.data) & 15) || (dst.nb[1] % 16) || (dst.nb[2] % 16) || (((uintptr_t) dst.data) & 15)) return false;
     if (mask && ((mask->nb[1] % 8) || (((uintptr_t) mask->data) & 7))) return false;
     return true;
+}
+// head size 256: 68 608 bytes of tiles + the tile states — above the 64 KB default for dynamic LDS, raised once per (form, device) to the most a launch can ask for
+template <int NW, bool CAP>
+static void launch_mma_d256(hipStream_t s, const dim3 grid, const size_t vt_bytes, const tdesc & q, const tdesc & k, const tdesc & v, const tdesc & mk, const tdesc & dst, const fam_geom & geo, float * ws,
+                            const uint8_t * tile_vis) {
+    constexpr size_t tiles_lds = 64 * (256 + 8) * 2 + 256 * (64 + 4) * 2;
+    static std::atomic<uint32_t> lds_raised{0};  // one bit per device (common.h: ensure_dyn_lds)
+    (void) ensure_dyn_lds((const void *) k_fattn_mma<256, NW, CAP>, tiles_lds + 16384, lds_raised);  // (at most 16 384 tile states: below; on failure the launch fails and graph_compute reports it)
+    hipLaunchKernelGGL((k_fattn_mma<256, NW, CAP>), grid, dim3(NW * 64), tiles_lds + vt_bytes, s, q, k, v, mk, dst, geo, ws, tile_vis);
 }
 bool launch_flash_attn_mma(hipStream_t s, const tdesc & q, const tdesc & k, const tdesc & v, const tdesc * mask, const float * sinks, const tdesc & dst,
                            const fattn_params & p, void * workspace) {
@@ -631,7 +934,9 @@ bool launch_flash_attn_mma(hipStream_t s, const tdesc & q, const tdesc & k, cons
     geo.n_kv_head = (int) k.ne[2];
     geo.n_kv = (int) k.ne[1];
     geo.has_mask = mask ? 1 : 0;
-    geo.scale = p.scale;
+    const bool cap = p.logit_softcap != 0.0f;
+    geo.scale = cap ? p.scale / p.logit_softcap : p.scale;
+    geo.softcap = p.logit_softcap;
     geo.n_splits = std::max(1, p.n_splits);
     const tdesc mk = mask ? *mask : q;
     float * ws = (float *) workspace;
@@ -641,7 +946,10 @@ bool launch_flash_attn_mma(hipStream_t s, const tdesc & q, const tdesc & k, cons
     const uint8_t * const tile_vis = tps <= 16384 ? p.tile_vis : nullptr;  // (without the states every tile is multiplied and reads its mask: correct, slower)
     const size_t vt_bytes = tile_vis ? (size_t) ((tps + 15) & ~15) : 0;  // the split's tile states (a byte per tile)
     g_fa_form = fa_form_code(FA_FORM_K_MMA, tile_vis ? 1 : 0, nw, FA_FORM_KV_F16, D, FA_FORM_TAIL_NONE);  // (the combine pass adds which kernel merges)
-    if (D == 128) {
+    if (D == 256) {
+        if (nw == 4) { if (cap) launch_mma_d256<4, true>(s, grid, vt_bytes, q, k, v, mk, dst, geo, ws, tile_vis); else launch_mma_d256<4, false>(s, grid, vt_bytes, q, k, v, mk, dst, geo, ws, tile_vis); }
+        else { if (cap) launch_mma_d256<2, true>(s, grid, vt_bytes, q, k, v, mk, dst, geo, ws, tile_vis); else launch_mma_d256<2, false>(s, grid, vt_bytes, q, k, v, mk, dst, geo, ws, tile_vis); }
+    } else if (D == 128) {
         const size_t lds = 64 * (128 + 8) * 2 + 128 * (64 + 4) * 2 + vt_bytes;
         if (nw == 4) hipLaunchKernelGGL((k_fattn_mma<128, 4>), grid, dim3(256), lds, s, q, k, v, mk, dst, geo, ws, tile_vis);
         else hipLaunchKernelGGL((k_fattn_mma<128, 2>), grid, dim3(128), lds, s, q, k, v, mk, dst, geo, ws, tile_vis);
@@ -673,7 +981,7 @@ size_t attn_nf_mma_ws_bytes(const tdesc & q, int n_splits) {  // [statistics: ro
 // dst: the result as [D, head, token] strides in nb[1] (head) / nb[2] (token) — the caller passes kqv's or the CONT copy's layout that way
 void launch_attn_nf_mma(hipStream_t s, const tdesc & q, const tdesc & k, const tdesc & vt, const tdesc & mask, const tdesc & dst, float scale, int n_splits, const uint8_t * tile_vis, void * workspace,
                         void * q8_out) {
-    fam_geom geo;
+    fam_geom geo{};
     geo.n_q = (int) q.ne[1];
     geo.n_head = (int) q.ne[2];
     geo.n_kv_head = (int) k.ne[2];

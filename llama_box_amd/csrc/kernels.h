@@ -386,15 +386,20 @@ void launch_flash_attn_combine(hipStream_t s, int D, const float * ws, const flo
 // The note is per host thread (a backend's graph walk runs on one thread; in-process tensor parallel walks on several); graph.cpp clears it in front of a
 // FLASH_ATTN_EXT node's launch and copies it into that backend's stats behind it — the combine pass of the non-flash chain writes the thread's note too, which
 // nobody copies.  The stat is 0 for a graph without such a node; a replayed hipGraph reports what its capture walk noted.
-//   bits 0..3 kernel, 4..5 mode, 6..9 waves per workgroup, 10..11 cache kind, bit 12 head size 128 (clear: 64), bits 13..15 what merges the split records
+//   bits 0..3 kernel, 4..5 mode, 6..9 waves per workgroup, 10..11 cache kind, bit 12 head size 128 (clear: 64), bits 13..15 what merges the split records,
+//   bit 16 head size 256 (bit 12 is clear then; every code of a head-size-64 / -128 form keeps the value it had before that bit existed)
 // (tests/fa_ref.py parses these names and values)
 enum {
     FA_FORM_K_SPLIT = 1, FA_FORM_K_DEC = 2, FA_FORM_K_MMA = 3,                                    // k_fattn_split / k_fattn_dec128 / k_fattn_mma
     FA_FORM_MODE_PLAIN = 0, FA_FORM_MODE_SKIP = 1, FA_FORM_MODE_LIST = 2,                         // k_fattn_dec128's MODE; k_fattn_mma: 1 = with tile states
     FA_FORM_KV_F16 = 0, FA_FORM_KV_Q8_0 = 1, FA_FORM_KV_BLOCK = 2, FA_FORM_KV_Q8_IMAGE = 3,       // f16 cache, block_q8_0 in place, another block format in place, q8_0 through its f16 image
     FA_FORM_TAIL_NONE = 0, FA_FORM_TAIL_COMBINE = 1, FA_FORM_TAIL_COMBINE_ROWS = 2, FA_FORM_TAIL_SELF_MERGE = 3, FA_FORM_TAIL_MERGE2 = 4, FA_FORM_TAIL_FAT = 5,
+    FA_FORM_D256_BIT = 16,  // the bit (not a field value) that says head size 256
 };
-static inline int fa_form_code(int kernel, int mode, int waves, int kv, int D, int tail) { return kernel | (mode << 4) | (waves << 6) | (kv << 10) | ((D == 128 ? 1 : 0) << 12) | (tail << 13); }
+static inline int fa_form_code(int kernel, int mode, int waves, int kv, int D, int tail) {
+    if (D == 256) kernel |= 1 << FA_FORM_D256_BIT;
+    return kernel | (mode << 4) | (waves << 6) | (kv << 10) | ((D == 128 ? 1 : 0) << 12) | (tail << 13);
+}
 extern thread_local int g_fa_form;  // (fattn.hip)
 
 // ---- the decode copy (repack.hip): rows [r0, r0 + n_rows) of a K-quant [K, N] matrix from the block layout at `src` into the plane layout at `dst` (same row stride)
