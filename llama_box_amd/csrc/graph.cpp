@@ -1723,6 +1723,7 @@ static bool try_fuse_attn_nf(exec_state & st, int i) {
         c->st.fused_nodes++;
     }
     c->st.kernel_launches++;
+    c->st.nf_list_chains++;
     mark_done(st, js);
     mark_done(st, jv);
     c->st.fused_nodes += 2;

@@ -100,6 +100,7 @@ inline void options_from_env(options & o) {
     X(wide_launches)              /* prompt-batch mat-muls served by its wide form */                                                                                    \
     X(tiled_launches)             /* batch mat-muls served by the LDS-tiled int8 GEMM (mmq_i8.hip) */                                                                    \
     X(nf_mma_chains)              /* non-flash K.q -> SOFT_MAX -> V^T.p chains of a prompt micro-batch served by the two-pass matrix-core kernel (round 4) */            \
+    X(nf_list_chains)             /* ... and those of a 2..32-token batch served by the one-launch list kernel (attn_nf.hip) */                                          \
     X(fa_form)                    /* kernels.h fa_form_code of the last FLASH_ATTN_EXT node of the graph computed last (0: it had none) */                               \
     X(fa_list_launches)           /* FLASH_ATTN_EXT nodes served over per-token position lists (2..32 tokens; 33..256 when the mask is known to be sparse) */            \
     X(rope_epilogues)             /* batches whose rope + KV-cache stores rode in the skinny QKV launches */                                                             \

@@ -2,6 +2,7 @@
 //   rows                 one line per option: key type default env-name-or-dash
 //   env                  options_from_env over the defaults, then one line per option: key value
 //   set K=V [K=V ...]    options_set one after the other on default options; after each a line: rc=<0|1> eq=<equal to the defaults> then every key=value
+//   stats                one line per counter of a fresh backend: key value
 //   helpers              env_flag / env_int / env_present against the four getenv idioms they replace, over unset, "", 0, 1, 2, x (exit 1 on a difference)
 #include <cstdio>
 #include <cstdlib>
@@ -62,7 +63,14 @@ int main(int argc, char ** argv) {
         }
         return 0;
     }
+    if (cmd == "stats") {
+        const stats st;
+#define MI_X(name) { const int64_t * v = stats_find(st, #name); printf("%s %lld\n", #name, v == &st.name ? (long long) *v : -1LL); }
+        MI_STATS(MI_X)
+#undef MI_X
+        return stats_find(st, "no_such_stat") ? 1 : 0;
+    }
     if (cmd == "helpers") return helpers();
-    fprintf(stderr, "usage: options_probe rows | env | set K=V ... | helpers\n");
+    fprintf(stderr, "usage: options_probe rows | env | set K=V ... | stats | helpers\n");
     return 2;
 }

@@ -15,7 +15,7 @@ OPTION_DEFAULTS = {
 }
 STAT_KEYS = [
     "graph_launches", "graph_captures", "eager_graphs", "kernel_launches", "fused_nodes", "allreduces", "ss_handoffs", "fa_list_launches", "fa_form",
-    "nf_mma_chains", "p2p_allreduces", "p2p_timeouts", "step_heads", "elided_conts", "decode_copy_tensors", "decode_copy_bytes", "decode_copy_launches",
+    "nf_mma_chains", "nf_list_chains", "p2p_allreduces", "p2p_timeouts", "step_heads", "elided_conts", "decode_copy_tensors", "decode_copy_bytes", "decode_copy_launches",
     "graph_exec_update_failures", "graph_evictions", "graph_cache_size", "graph_launch_host_ns", "kernel_downloads", "kv_image_nodes", "kv_native_nodes",
     "graph_key_host_ns", "graph_compute_host_ns", "graph_key_fast_hits", "graph_key_collisions", "graph_early_captures", "graph_shadow_captures",
     "graph_capture_walk_ns", "graph_exec_update_ns", "graph_shadow_eager_ns", "graph_exec_updates", "skinny_launches", "mmid_launches", "wide_launches",

@@ -126,6 +126,17 @@ def test_unknown_and_empty_keys_are_refused(probe):
         assert parse_set(ln) == (0, 1, DEFAULTS)
 
 
+# counters hosts and tests read through get_stat, as they spell them (the whole list as a backend answers it: tests/test_gpu_option_keys.py)
+STAT_KEYS = ["graph_launches", "kernel_launches", "fused_nodes", "nf_mma_chains", "nf_list_chains", "fa_form", "fa_list_launches", "skinny_launches", "mmid_launches"]
+
+
+def test_stat_keys_are_in_the_table_and_start_at_zero(probe):
+    got = fields(probe("stats"))
+    assert all(v == 0 for v in got.values()), got  # (-1: stats_find does not return the counter of that name)
+    for key in STAT_KEYS:
+        assert key in got, key
+
+
 def test_env_helpers_mean_what_the_spelled_out_reads_meant(probe):
     # value: env_flag(name, true), env_flag(name, false), env_int(name, 7), env_present(name) — and "same" = equal to the four getenv idioms the probe spells out
     want = {"unset": (1, 0, 7, 0), "empty": (0, 0, 0, 1), "0": (0, 0, 0, 1), "1": (1, 1, 1, 1), "2": (1, 1, 2, 1), "x": (0, 0, 0, 1)}
