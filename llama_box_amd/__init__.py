@@ -133,6 +133,7 @@ _SIGS = {
     "ggml_flash_attn_ext_add_sinks": (None, [TP, TP]), "ggml_argmax": (TP, [_P, TP]),
     "ggml_argsort": (TP, [_P, TP, _I]), "ggml_top_k": (TP, [_P, TP, _I]), "ggml_sum_rows": (TP, [_P, TP]), "ggml_clamp": (TP, [_P, TP, _F, _F]),
     "ggml_mul_mat_id": (TP, [_P, TP, TP, TP]),
+    "ggml_concat": (TP, [_P, TP, TP, _I]), "ggml_ssm_conv": (TP, [_P, TP, TP]), "ggml_ssm_scan": (TP, [_P, TP, TP, TP, TP, TP, TP, TP]),
     "ggml_new_graph": (C.POINTER(CGraph), [_P]), "ggml_new_graph_custom": (C.POINTER(CGraph), [_P, _SZ, _B]),
     "ggml_build_forward_expand": (None, [C.POINTER(CGraph), TP]), "ggml_graph_n_nodes": (_I, [C.POINTER(CGraph)]),
     "ggml_graph_node": (TP, [C.POINTER(CGraph), _I]), "ggml_graph_view": (CGraph, [C.POINTER(CGraph), _I, _I]),

@@ -245,6 +245,55 @@ static bool glu_rows_dense(const ggml_tensor * t) { return t->nb[2] == t->nb[1] 
 static bool is_gelu_op(int u) { return u == GGML_UNARY_OP_GELU || u == GGML_UNARY_OP_GELU_QUICK || u == GGML_UNARY_OP_GELU_ERF; }
 static bool is_act_glu_op(int o) { return o == GGML_GLU_OP_REGLU || o == GGML_GLU_OP_GEGLU || o == GGML_GLU_OP_GEGLU_QUICK || o == GGML_GLU_OP_GEGLU_ERF; }
 
+// The three ops of a state-space layer (ssm.hip; DESIGN.md §4i restates their contracts).  Shapes, types and strides only.
+// CONCAT: f32 / i32 / f16, the sources of one type with any (element-aligned) strides and equal extents off `dim`, the result contiguous
+static bool concat_ok(const ggml_tensor * op) {
+    const ggml_tensor * a = op->src[0];
+    const ggml_tensor * b = op->src[1];
+    const int dim = op->op_params[0];
+    if (!a || !b || dim < 0 || dim > 3 || a->type != b->type || op->type != a->type || !ggml_abi_is_contiguous(op)) return false;
+    if (a->type != GGML_TYPE_F32 && a->type != GGML_TYPE_I32 && a->type != GGML_TYPE_F16) return false;
+    const size_t ts = ggml_abi_type_size(a->type);
+    for (int d = 0; d < 4; ++d) {
+        if (a->nb[d] % ts || b->nb[d] % ts) return false;
+        if (d == dim ? op->ne[d] != a->ne[d] + b->ne[d] : (a->ne[d] != b->ne[d] || op->ne[d] != a->ne[d])) return false;
+    }
+    return true;
+}
+// SSM_CONV: sx f32 [d_conv - 1 + n_t, d_inner, n_s] with dense rows (nb1 = ne0 * 4; nb2 free), c f32 [d_conv, d_inner], d_conv 2 .. 8 -> f32 [d_inner, n_t, n_s] contiguous
+static bool ssm_conv_ok(const ggml_tensor * op) {
+    const ggml_tensor * sx = op->src[0];
+    const ggml_tensor * c = op->src[1];
+    if (!sx || !c || sx->type != GGML_TYPE_F32 || c->type != GGML_TYPE_F32 || !is_f32_contig(op)) return false;
+    const int64_t d_conv = c->ne[0], d_inner = c->ne[1], n_t = sx->ne[0] - d_conv + 1;
+    if (d_conv < 2 || d_conv > 8 || n_t < 0 || c->ne[2] != 1 || c->ne[3] != 1 || sx->ne[1] != d_inner || sx->ne[3] != 1) return false;
+    if (sx->nb[0] != 4 || sx->nb[1] != (size_t) sx->ne[0] * 4 || (sx->nb[2] % 4) || c->nb[0] != 4 || (c->nb[1] % 4)) return false;
+    if (ggml_abi_nelements(op) > ((int64_t) 1 << 38)) return false;  // (one thread an element, 256 a workgroup: the grid's x extent)
+    return op->ne[0] == d_inner && op->ne[1] == n_t && op->ne[2] == sx->ne[2] && op->ne[3] == 1;
+}
+// SSM_SCAN: src = {s, x, dt, A, B, C, ids}.  d_state 16 / 64 / 128 / 256; A per head ([1, n_head], Mamba-2) or per state element ([d_state, n_head], Mamba-1);
+// n_group 1 or n_head — between the two, which heads share a group is not pinned by anything on record, so those graphs are refused
+static bool ssm_scan_ok(const ggml_tensor * op) {
+    const ggml_tensor * s = op->src[0], * x = op->src[1], * dt = op->src[2], * A = op->src[3], * B = op->src[4], * C = op->src[5], * ids = op->src[6];
+    if (!s || !x || !dt || !A || !B || !C || !ids) return false;
+    for (const ggml_tensor * t : {s, x, dt, A, B, C, op}) if (t->type != GGML_TYPE_F32) return false;
+    if (ids->type != GGML_TYPE_I32 || !ggml_abi_is_contiguous(ids)) return false;
+    if (!ggml_abi_is_contiguous(s) || !ggml_abi_is_contiguous(dt) || !ggml_abi_is_contiguous(A) || !ggml_abi_is_contiguous(op)) return false;
+    const int64_t d_state = s->ne[0], head_dim = x->ne[0], n_head = x->ne[1], n_t = x->ne[2], n_s = x->ne[3], n_group = B->ne[1];
+    if (d_state != 16 && d_state != 64 && d_state != 128 && d_state != 256) return false;
+    if (head_dim < 1 || n_head < 1 || s->ne[1] != head_dim || s->ne[2] != n_head || (n_s > 0 && s->ne[3] < 1)) return false;
+    if (n_t < 1 && n_s > 0) return false;  // (no token: the launch would leave the result's state area unwritten; llama.cpp builds no such node)
+    if (n_group != 1 && n_group != n_head) return false;
+    if (x->nb[0] != 4 || x->nb[1] != (size_t) head_dim * 4 || (x->nb[2] % 4) || (x->nb[3] % 4)) return false;
+    for (const ggml_tensor * t : {B, C})
+        if (t->ne[0] != d_state || t->ne[1] != n_group || t->ne[2] != n_t || t->ne[3] != n_s || t->nb[0] != 4 || t->nb[1] != (size_t) d_state * 4 || (t->nb[2] % 4) || (t->nb[3] % 4)) return false;
+    if (dt->ne[0] != n_head || dt->ne[1] != n_t || dt->ne[2] != n_s || dt->ne[3] != 1) return false;
+    if ((A->ne[0] != 1 && A->ne[0] != d_state) || A->ne[1] != n_head || A->ne[2] != 1 || A->ne[3] != 1) return false;
+    if (ggml_abi_nelements(ids) != n_s || ids->ne[0] != n_s) return false;
+    if (n_s > 65535 || n_t > INT32_MAX / 2 || s->ne[3] > INT32_MAX / 2 || head_dim * n_head > INT32_MAX / 512) return false;  // (grid.y; the kernel's int row and token indices)
+    return ggml_abi_nelements(op) == ggml_abi_nelements(x) + d_state * head_dim * n_head * n_s && op->ne[0] == ggml_abi_nelements(op);
+}
+
 bool supports_op(const ggml_tensor * op) {
     const ggml_tensor * a = op->src[0];
     const ggml_tensor * b = op->src[1];
@@ -334,6 +383,12 @@ bool supports_op(const ggml_tensor * op) {
             return fa_route(op) != 0;
         case GGML_OP_ARGMAX:
             return a->type == GGML_TYPE_F32 && a->nb[0] == 4;
+        case GGML_OP_CONCAT:
+            return concat_ok(op);
+        case GGML_OP_SSM_CONV:
+            return ssm_conv_ok(op);
+        case GGML_OP_SSM_SCAN:
+            return ssm_scan_ok(op);
         default:
             return false;
     }
@@ -957,6 +1012,35 @@ static norm_affine find_norm_affine(const exec_state & st, int i) {
         f.out = cur = t;
         f.absorbed = k;
     }
+    return f;
+}
+
+// SSM_CONV n (node i) -> ADD(n, bias [d_inner]) -> UNARY(SILU): the conv1d of a Mamba layer with its bias and activation (llama.cpp build_mamba_layer /
+// build_mamba2_layer).  k_ssm_conv adds the bias and applies silu_f itself, each with the rounding of the node it stands for, and writes the UNARY's tensor.  The
+// guards are find_norm_affine's: each absorbed result has one reader and is no output, the bias is an f32 row of d_inner values and nothing more, the shape is kept
+// — and the memory written (a LATER node's, which the host allocator may have cut from a recycled block) is apart from everything the launch reads.
+struct ssm_conv_act {
+    const ggml_tensor * bias = nullptr;
+    const ggml_tensor * out = nullptr;  // the tensor the launch writes: n or the UNARY
+    int absorbed = 0;                   // 0 or 2
+};
+static ssm_conv_act find_ssm_conv_act(const exec_state & st, int i) {
+    const ggml_cgraph * g = st.g;
+    const ggml_tensor * n = g->nodes[i];
+    ssm_conv_act f;
+    f.out = n;
+    if (i + 2 >= g->n_nodes || st.done[i + 1] || st.done[i + 2]) return f;
+    const ggml_tensor * add = g->nodes[i + 1];
+    const ggml_tensor * act = g->nodes[i + 2];
+    if (add->op != GGML_OP_ADD || add->src[0] != n || act->op != GGML_OP_UNARY || act->op_params[0] != GGML_UNARY_OP_SILU || act->src[0] != add) return f;
+    if (!single_use(st, n) || !single_use(st, add)) return f;
+    const ggml_tensor * v = add->src[1];
+    if (!v || v->type != GGML_TYPE_F32 || !ggml_abi_is_contiguous(v) || v->ne[0] != n->ne[0] || ggml_abi_nelements(v) != v->ne[0]) return f;
+    if (!is_f32_contig(add) || !is_f32_contig(act) || !same_shape(add, n) || !same_shape(act, n)) return f;
+    if (ranges_overlap(act, n->src[0]) || ranges_overlap(act, n->src[1]) || ranges_overlap(act, v)) return f;
+    f.bias = v;
+    f.out = act;
+    f.absorbed = 2;
     return f;
 }
 
@@ -2442,6 +2526,28 @@ static int run_node(exec_state & st, int i) {
             launch_argmax(s, TD(a), TD(n));
             c->st.kernel_launches++;
             return 1;
+        case GGML_OP_CONCAT: {
+            timed_scope ts(c, "concat", (double) ggml_abi_nbytes(n) * 2);
+            if (!launch_concat(s, TD(a), TD(b), TD(n), n->op_params[0])) return -1;
+            c->st.kernel_launches++;
+            return 1;
+        }
+        case GGML_OP_SSM_CONV: {
+            // SSM_CONV -> ADD(bias) -> UNARY(SILU): one kernel writing the UNARY's output
+            const ssm_conv_act f = (fuse && c->ssm_fuse) ? find_ssm_conv_act(st, i) : ssm_conv_act{nullptr, n, 0};
+            timed_scope ts(c, f.absorbed ? "ssm_conv_bias_silu" : "ssm_conv", (double) ggml_abi_nbytes(a) + (double) ggml_abi_nbytes(n));
+            if (!launch_ssm_conv(s, TD(a), TD(b), TD(f.out), f.bias ? (const float *) f.bias->data : nullptr)) return -1;
+            c->st.kernel_launches++;
+            c->st.fused_nodes += f.absorbed;
+            return 1 + f.absorbed;
+        }
+        case GGML_OP_SSM_SCAN: {
+            // (bytes: the states read and written; x, dt, B, C and y are small beside them at decode)
+            timed_scope ts(c, "ssm_scan", (double) (ggml_abi_nelements(n) - ggml_abi_nelements(b)) * 8);
+            if (!launch_ssm_scan(s, TD(a), TD(b), TD(n->src[2]), TD(n->src[3]), TD(n->src[4]), TD(n->src[5]), TD(n->src[6]), TD(n))) return -1;
+            c->st.kernel_launches++;
+            return 1;
+        }
         default:
             MI_ERR("graph_compute: unsupported op %d (node %d '%s')", (int) n->op, i, n->name);
             return -1;

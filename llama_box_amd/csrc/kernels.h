@@ -408,6 +408,14 @@ void launch_repack_planes(hipStream_t s, int type, const void * src, void * dst,
 bool repack_q80_supported(int type, int64_t K, int64_t N, int64_t nb1);  // Q8_0: the panel copy of the 9 .. 32-column matrix-core kernel (repack.hip)
 void launch_repack_q80_panels(hipStream_t s, const void * src, void * dst, int64_t K, int64_t N, int64_t nb1);
 
+// ---- state-space layers (ssm.hip).  Every launcher returns true without launching when its grid is empty; false = a shape supports_op refuses
+// CONCAT along `dim`: an exact element copy, sources with any strides, dst contiguous (f32 / i32 / f16)
+bool launch_concat(hipStream_t s, const tdesc & a, const tdesc & b, const tdesc & dst, int dim);
+// SSM_CONV, d_conv 2 .. 8; bias != nullptr: dst = silu(conv + bias[i1]) — the ADD and UNARY(SILU) nodes behind it, with their roundings
+bool launch_ssm_conv(hipStream_t s, const tdesc & sx, const tdesc & c, const tdesc & dst, const float * bias);
+// SSM_SCAN, d_state 16 / 64 / 128 / 256, n_group 1 or n_head; dst: y, then the final states in sequence order
+bool launch_ssm_scan(hipStream_t s, const tdesc & st, const tdesc & x, const tdesc & dt, const tdesc & A, const tdesc & B, const tdesc & C, const tdesc & ids, const tdesc & dst);
+
 // ---- code-object preload (round 4).  The HIP runtime loads a translation unit's device code on the FIRST launch of one of its kernels
 // (0.3 - 2 ms each, measured as idle gaps in front of the first prompt's kernels: 5.5 ms of a 64 ms prefill).  Every kernel file ends with
 // MI_TU_TOUCH(name): an empty kernel + a launcher; init_backend launches them all once per device, so the cost moves to start-up.
@@ -432,6 +440,7 @@ void tu_touch_tp_p2p(hipStream_t s);
 void tu_touch_kv_types(hipStream_t s);
 void tu_touch_repack(hipStream_t s);
 void tu_touch_mmid(hipStream_t s);
+void tu_touch_ssm(hipStream_t s);
 inline void preload_kernel_files(hipStream_t s) {
     tu_touch_kv_types(s);
     tu_touch_repack(s);
@@ -451,6 +460,7 @@ inline void preload_kernel_files(hipStream_t s) {
     tu_touch_fattn(s);
     tu_touch_fattn_mma(s);
     tu_touch_tp_p2p(s);
+    tu_touch_ssm(s);
 }
 
 }  // namespace mi355x

@@ -59,6 +59,10 @@ namespace mi355x {
     X(int, shadow_capture, 1, 0, 1)    /* a capture at first sighting runs BEHIND the step's own eager launches */                                                       \
     X(int, q80_min_cols, 33, 0, 1)     /* Q8_0 weights: batches of at least this many columns take the matrix-core GEMM (mmq_q80.hip), smaller ones 8-column mat-vec passes */
 
+// One per-backend switch is kept beside the table: ssm_fuse (backend_ctx::ssm_fuse, default on, GGML_MI355X_SSM_FUSE, set_option("ssm_fuse", 0 / 1)): SSM_CONV ->
+// ADD(bias) -> SILU as one launch.  tests/test_options_host.py holds the table's rows as a written-down contract that is extended on purpose, in a change of its own;
+// until then the switch is no row: backend.cpp reads the variable and stores the value next to the keys that are no field of c->opt.
+
 struct options {
 #define MI_X(type, name, def, flag, env) type name = def;
     MI_OPTIONS(MI_X)

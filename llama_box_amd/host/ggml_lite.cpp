@@ -591,6 +591,63 @@ struct ggml_tensor * ggml_mul_mat_id(struct ggml_context * ctx, struct ggml_tens
     return r;
 }
 
+// state-space layers (llama.cpp build_mamba_layer / build_mamba2_layer)
+struct ggml_tensor * ggml_concat(struct ggml_context * ctx, struct ggml_tensor * a, struct ggml_tensor * b, int dim) {
+    LITE_ASSERT(dim >= 0 && dim < GGML_MAX_DIMS);
+    LITE_ASSERT(a->type == b->type);
+    int64_t ne[GGML_MAX_DIMS];
+    for (int d = 0; d < GGML_MAX_DIMS; ++d) {
+        if (d == dim) { ne[d] = a->ne[d] + b->ne[d]; continue; }
+        LITE_ASSERT(a->ne[d] == b->ne[d]);
+        ne[d] = a->ne[d];
+    }
+    ggml_tensor * r = ggml_new_tensor(ctx, a->type, GGML_MAX_DIMS, ne);
+    r->op_params[0] = dim;
+    r->op = GGML_OP_CONCAT;
+    r->src[0] = a;
+    r->src[1] = b;
+    return r;
+}
+struct ggml_tensor * ggml_ssm_conv(struct ggml_context * ctx, struct ggml_tensor * sx, struct ggml_tensor * c) {
+    LITE_ASSERT(sx->ne[3] == 1);                         // sx is 3-D
+    LITE_ASSERT(c->ne[2] == 1 && c->ne[3] == 1);         // c is a matrix
+    const int64_t d_conv = c->ne[0], d_inner = c->ne[1];
+    const int64_t n_t = sx->ne[0] - d_conv + 1, n_s = sx->ne[2];
+    LITE_ASSERT(sx->ne[0] == d_conv - 1 + n_t);
+    LITE_ASSERT(sx->ne[1] == d_inner);
+    LITE_ASSERT(n_t >= 0);
+    ggml_tensor * r = ggml_new_tensor_3d(ctx, GGML_TYPE_F32, d_inner, n_t, n_s);
+    r->op = GGML_OP_SSM_CONV;
+    r->src[0] = sx;
+    r->src[1] = c;
+    return r;
+}
+struct ggml_tensor * ggml_ssm_scan(struct ggml_context * ctx, struct ggml_tensor * s, struct ggml_tensor * x, struct ggml_tensor * dt, struct ggml_tensor * A,
+                                   struct ggml_tensor * B, struct ggml_tensor * C, struct ggml_tensor * ids) {
+    LITE_ASSERT(ggml_is_contiguous(s) && ggml_is_contiguous(dt) && ggml_is_contiguous(A));
+    LITE_ASSERT(x->nb[0] == ggml_type_size(x->type) && B->nb[0] == ggml_type_size(B->type) && C->nb[0] == ggml_type_size(C->type));
+    LITE_ASSERT(x->nb[1] == (size_t) x->ne[0] * x->nb[0] && B->nb[1] == (size_t) B->ne[0] * B->nb[0] && C->nb[1] == (size_t) C->ne[0] * C->nb[0]);
+    for (int d = 0; d < GGML_MAX_DIMS; ++d) LITE_ASSERT(B->ne[d] == C->ne[d]);
+    LITE_ASSERT(ids->type == GGML_TYPE_I32);
+    const int64_t d_state = s->ne[0], head_dim = x->ne[0], n_head = x->ne[1], n_t = x->ne[2], n_s = x->ne[3];
+    LITE_ASSERT(s->ne[1] == head_dim && s->ne[2] == n_head);
+    LITE_ASSERT(B->ne[0] == d_state && B->ne[2] == n_t && B->ne[3] == n_s);
+    LITE_ASSERT(n_head % B->ne[1] == 0);
+    LITE_ASSERT(dt->ne[0] == n_head && dt->ne[1] == n_t && dt->ne[2] == n_s && dt->ne[3] == 1);
+    LITE_ASSERT((A->ne[0] == 1 || A->ne[0] == d_state) && A->ne[1] == n_head && A->ne[2] == 1 && A->ne[3] == 1);
+    LITE_ASSERT(ids->ne[0] == n_s && ids->ne[1] == 1 && ids->ne[2] == 1 && ids->ne[3] == 1);
+    ggml_tensor * r = ggml_new_tensor_1d(ctx, GGML_TYPE_F32, ggml_nelements(x) + d_state * head_dim * n_head * n_s);  // y, then the final states in sequence order
+    r->op = GGML_OP_SSM_SCAN;
+    r->src[0] = s;
+    r->src[1] = x;
+    r->src[2] = dt;
+    r->src[3] = A;
+    r->src[4] = B;
+    r->src[5] = C;
+    r->src[6] = ids;
+    return r;
+}
+
 // ------------------------------------------------------------------------------------------------ graphs
 struct ggml_cgraph * ggml_new_graph_custom(struct ggml_context * ctx, size_t size, bool) {
     ggml_cgraph * g = new ggml_cgraph();

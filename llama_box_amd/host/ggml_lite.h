@@ -127,6 +127,14 @@ struct ggml_tensor * ggml_sum_rows(struct ggml_context * ctx, struct ggml_tensor
 struct ggml_tensor * ggml_clamp(struct ggml_context * ctx, struct ggml_tensor * a, float min, float max);  /* in place: a view of a */
 /* as [K, N, n_expert], b [K, n_used | 1, n_tokens] f32, ids [n_used, n_tokens] i32 -> [N, n_used, n_tokens] */
 struct ggml_tensor * ggml_mul_mat_id(struct ggml_context * ctx, struct ggml_tensor * as, struct ggml_tensor * b, struct ggml_tensor * ids);
+/* state-space layers (llama.cpp build_mamba_layer / build_mamba2_layer; DESIGN.md §4i states the three contracts) */
+struct ggml_tensor * ggml_concat(struct ggml_context * ctx, struct ggml_tensor * a, struct ggml_tensor * b, int dim);
+/* sx [d_conv - 1 + n_t, d_inner, n_s], c [d_conv, d_inner] -> [d_inner, n_t, n_s] */
+struct ggml_tensor * ggml_ssm_conv(struct ggml_context * ctx, struct ggml_tensor * sx, struct ggml_tensor * c);
+/* s [d_state, head_dim, n_head, n_rs], x [head_dim, n_head, n_t, n_s], dt [n_head, n_t, n_s], A [d_state | 1, n_head], B / C [d_state, n_group, n_t, n_s],
+ * ids i32 [n_s] -> one f32 vector: y [head_dim, n_head, n_t, n_s], then the final states [d_state, head_dim, n_head, n_s] */
+struct ggml_tensor * ggml_ssm_scan(struct ggml_context * ctx, struct ggml_tensor * s, struct ggml_tensor * x, struct ggml_tensor * dt, struct ggml_tensor * A,
+                                   struct ggml_tensor * B, struct ggml_tensor * C, struct ggml_tensor * ids);
 
 /* graphs */
 struct ggml_cgraph * ggml_new_graph(struct ggml_context * ctx);
