@@ -258,6 +258,7 @@ void free_split_helpers(backend_ctx * c);
 
 // ---- graph execution (graph.cpp) ----
 bool supports_op(const ggml_tensor * op);
+bool mm_batched_q_ok(const ggml_tensor * op);  // MUL_MAT over a 3-D quantised weight, one matrix per head (mmb.hip): the whole operand contract
 enum ggml_status graph_compute(backend_ctx * ctx, ggml_cgraph * g);
 void free_graph_cache(backend_ctx * ctx);
 bool graph_key_equals(const ggml_cgraph * g, const std::vector<uint64_t> & key);  // the graph-key words (graph.cpp: walk_key), compared in place ...

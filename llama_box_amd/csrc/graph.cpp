@@ -176,6 +176,35 @@ static bool mm_cache_image_ok(const ggml_tensor * op) {
 // there, the image of a large view was written past the end of the scratch
 static bool mm_runs_on_image(const ggml_tensor * n) { return mm_cache_image_ok(n) && !buffer_is_split(n->src[0]->buffer); }
 
+// MUL_MAT over a 3-D quantised WEIGHT, one matrix per head (mmb.hip): the absorbed MLA matrices wk_b / wv_b of llama.cpp's deepseek2 graph.
+//   a [K, N, H, 1] Q8_0, Q4_0, Q4_1, Q5_0, Q5_1, IQ4_NL, Q4_K, Q5_K or Q6_K, rows contiguous, H >= 2 — rooted in a WEIGHTS buffer, or a plain tensor while the
+//     loader probes (what mm_cache_image_ok takes is excluded here: a block-format batch outside a weights buffer is a KV-cache view and keeps its f16 image);
+//   b [K, M, H * r2, E] f32, rows contiguous, dims 1 .. 3 at any element-aligned stride (ggml_permute(q_nope, 0, 2, 1, 3) of a strided view: nb[1] > nb[2]);
+//   dst [N, M, H * r2, E] f32 contiguous:  dst(:, m, h, e) = a(:, :, h / r2) · q(b(:, m, h, e))
+// Q2_K / Q3_K / IQ4_XS (and bf16) batches stay refused: their 2-D acceptance was merged with tests that pin the 3-D refusal.  The split (-sm row) and row-parallel
+// buffer types keep refusing.  The whole contract is here: supports_op, run_node, plan_ws and the in-process tensor-parallel engine (which declines) ask nobody else.
+bool mm_batched_q_ok(const ggml_tensor * op) {
+    if (op->op != GGML_OP_MUL_MAT) return false;
+    const ggml_tensor * a = op->src[0];
+    const ggml_tensor * b = op->src[1];
+    if (!a || !b || b->type != GGML_TYPE_F32 || op->type != GGML_TYPE_F32 || !ggml_abi_is_contiguous(op)) return false;
+    if (mm_cache_image_ok(op)) return false;  // a KV-cache view (K.q of the non-flash path over a Q8_0 / 4- / 5-bit cache): the f16 image keeps it
+    // ... and whatever else lives in a buffer that is not a WEIGHTS buffer stays where it was before this node existed (a cache batch the image declines — dim 3 of b
+    // broadcast, say — was refused and still is); no buffer at all is the loader's probe
+    const ggml_backend_buffer_t root = a->view_src && a->view_src->buffer ? a->view_src->buffer : a->buffer;
+    if (root && root->usage != GGML_BACKEND_BUFFER_USAGE_WEIGHTS) return false;
+    if (!is_quant(a->type) || is_kq23_type(a->type) || is_iq4xs_type(a->type)) return false;
+    if (a->ne[2] < 2 || a->ne[3] != 1 || !rows_contig(a) || a->ne[0] < 1 || a->ne[1] < 1 || a->ne[0] % ggml_abi_blck_size(a->type) != 0) return false;
+    if (needs_layout_check(a->type) && !l32_layout_ok(a)) return false;  // (the aligned formats: base, nb[1], nb[2] at the block alignment; not row-parallel, not split)
+    if (weight_is_rowpar(a) || buffer_is_split(a->buffer)) return false;
+    if (b->ne[0] != a->ne[0] || b->nb[0] != 4 || (b->nb[1] % 4) || (b->nb[2] % 4) || (b->nb[3] % 4)) return false;
+    if (b->ne[1] < 1 || b->ne[2] < 1 || b->ne[3] < 1 || b->ne[2] % a->ne[2] != 0) return false;
+    // int indices in the kernel; grid y = column blocks (one column each at the narrowest), grid z = heads x dim 3; the quantiser's grid x = rows x chunks
+    if (a->ne[0] > INT32_MAX / 2 || a->ne[1] > INT32_MAX / 2 || b->ne[1] > 65535 || b->ne[2] * b->ne[3] > 65535) return false;
+    if (b->ne[1] * b->ne[2] * b->ne[3] * ((a->ne[0] + 255) / 256) > INT32_MAX / 2) return false;
+    return op->ne[0] == a->ne[1] && op->ne[1] == b->ne[1] && op->ne[2] == b->ne[2] && op->ne[3] == b->ne[3];
+}
+
 // which attention path serves this FLASH_ATTN_EXT node: 0 none (the host keeps it on the CPU backend), 1 the f16 kernels on the cache views in place,
 // 2 the lane-parallel kernel on block_q8_0 K / V, 3 the f16 kernels on an f16 IMAGE of whichever of K / V is kept in another type (kv_types.hip:
 // -ctk / -ctv q4_0, q4_1, q5_0, q5_1, iq4_nl, bf16, f32, mixed pairs, and q8_0 shapes route 2 does not take).  Head sizes 64, 128 and 256.
@@ -311,6 +340,7 @@ bool supports_op(const ggml_tensor * op) {
             if (!a || !b || b->type != GGML_TYPE_F32 || op->type != GGML_TYPE_F32 || !ggml_abi_is_contiguous(op)) return false;
             if (buffer_is_split(a->buffer)) return split_mul_mat_supported(op);  // -sm row weights: every device computes its rows (split.cpp)
             if (mm_cache_image_ok(op)) return true;
+            if (mm_batched_q_ok(op)) return true;
             if (is_quant(a->type)) {
                 if (needs_layout_check(a->type) && !l32_layout_ok(a)) return false;
                 return a->ne[2] == 1 && a->ne[3] == 1 && rows_contig(a) && b->nb[0] == 4 && a->ne[0] % ggml_abi_blck_size(a->type) == 0;
@@ -435,7 +465,10 @@ static ws_plan plan_ws(backend_ctx * c, const ggml_cgraph * g) {
     for (int i = 0; i < g->n_nodes; ++i) {
         const ggml_tensor * n = g->nodes[i];
         const bool mm_image = n->op == GGML_OP_MUL_MAT && mm_runs_on_image(n);
-        if (n->op == GGML_OP_MUL_MAT && is_quant(n->src[0]->type) && !mm_image) {
+        if (!mm_image && mm_batched_q_ok(n)) {  // one matrix per head (mmb.hip): every row of the 4-D b quantised once, M * H * r2 * E rows; no second area
+            const ggml_tensor * b = n->src[1];
+            p.act_bytes = std::max(p.act_bytes, quantized_act_bytes(act_kind(n->src[0]->type), b->ne[0], b->ne[1] * b->ne[2] * b->ne[3]));
+        } else if (n->op == GGML_OP_MUL_MAT && is_quant(n->src[0]->type) && !mm_image) {
             const ggml_tensor * b = n->src[1];
             const int64_t Mc = b->ne[1] * b->ne[2] * b->ne[3];
             // (2..32 columns: the skinny matrix-core kernel fetches 32 columns' worth of activation bytes whatever M is)
@@ -684,18 +717,23 @@ static bool single_use(const exec_state & st, const ggml_tensor * t) { return us
 
 // returns the device pointer of src1 quantised for weight type `wtype`, quantising only if the scratch does not
 // already hold exactly this tensor (Q/K/V and gate/up share their input)
-static const void * quantized_src1(exec_state & st, const ggml_tensor * b, int wtype) {  // (wtype MI_ACT_Q80_PANEL: Q8_0 blocks in the panel order of the 9 .. 32-column kernel)
+// keyed = false (the batched node's permuted b): the key (data, kind, nbytes) does not tell a tensor from its ggml_permute(0, 2, 1, 3) with ne[1] == ne[2] — same
+// address, same bytes, other rows in other places.  Such a b is quantised every time and leaves no key behind, rather than the key growing strides and extents
+// that every other caller (contiguous rows, one per column) would carry for nothing.  The 2-D callers keep the key as it was: a contiguous b (the batched node's
+// too) leaves (data, kind, nbytes) behind, and a later 2-D MUL_MAT over a permuted view of that very tensor would still take the cached rows — a hazard older than
+// this parameter, which no graph llama.cpp builds reaches (a mat-mul's src1 there is a tensor or a reshape of one, never a permutation of an earlier src1).
+static const void * quantized_src1(exec_state & st, const ggml_tensor * b, int wtype, bool keyed = true) {  // (wtype MI_ACT_Q80_PANEL: Q8_0 blocks in the panel order of the 9 .. 32-column kernel)
     backend_ctx * c = st.c;
     const int kind = (wtype == MI_ACT_Q80_PANEL || wtype == MI_ACT_Q81_PANEL) ? wtype : act_kind(wtype);
     void * dst = (char *) c->ws + st.act_off;
-    if (c->q8_src == b->data && c->q8_kind == kind && c->q8_bytes == ggml_abi_nbytes(b)) return dst;
+    if (keyed && c->q8_src == b->data && c->q8_kind == kind && c->q8_bytes == ggml_abi_nbytes(b)) return dst;
     {
         timed_scope ts(c, "quantize_act", (double) ggml_abi_nbytes(b));
         if (kind == MI_ACT_Q80_PANEL) launch_quantize_q80_panel(c->stream, TD(b), dst);
         else launch_quantize_act(c->stream, kind, TD(b), dst);
         c->st.kernel_launches++;
     }
-    c->q8_src = b->data;
+    c->q8_src = keyed ? b->data : nullptr;
     c->q8_kind = kind;
     c->q8_bytes = ggml_abi_nbytes(b);
     return dst;
@@ -736,7 +774,7 @@ static bool quant_consumers_only(const exec_state & st, int at, const ggml_tenso
     if ((t->flags & GGML_TENSOR_FLAG_OUTPUT) || t->type != GGML_TYPE_F32 || (t->ne[0] % 256) != 0 || t->ne[0] > 16384 * 4) return false;
     const int last = last_reader_if_all(st, at + 1, t, [&](const ggml_tensor * u, int s) {
         const ggml_tensor * wt = u->src[0];
-        return u->op == GGML_OP_MUL_MAT && s == 1 && (wt->type == GGML_TYPE_Q4_K || wt->type == GGML_TYPE_Q5_K || wt->type == GGML_TYPE_Q6_K) &&
+        return u->op == GGML_OP_MUL_MAT && s == 1 && (wt->type == GGML_TYPE_Q4_K || wt->type == GGML_TYPE_Q5_K || wt->type == GGML_TYPE_Q6_K) && wt->ne[2] == 1 && wt->ne[3] == 1 &&
                !buffer_is_split(wt->buffer);  // (split weights read the f32 activations on other devices: the tensor itself must exist)
     });
     return last >= 0 && act_area_kept_for(st, at, last, t);
@@ -1999,6 +2037,32 @@ static int run_node(exec_state & st, int i) {
                 c->st.kernel_launches += 2;
                 c->st.kv_image_nodes++;
                 return 1;
+            }
+            if (mm_batched_q_ok(n)) {
+                // one quantised matrix per head (wk_b / wv_b of an MLA layer): the quantiser over every row of the 4-D b, then ONE launch for any M.  Shapes only:
+                // no host read, no epilogue, no prologue — the node captures like a dense mat-vec
+                mmb_args m{};
+                m.W = (const uint8_t *) a->data;
+                m.w_nb1 = (int64_t) a->nb[1];
+                m.w_nb2 = (int64_t) a->nb[2];
+                m.type = (int) a->type;
+                m.K = (int) a->ne[0];
+                m.N = (int) a->ne[1];
+                m.M = (int) b->ne[1];
+                m.Hb = (int) b->ne[2];
+                m.E = (int) b->ne[3];
+                m.r2 = (int) (b->ne[2] / a->ne[2]);
+                m.dst = (float *) n->data;
+                m.act = quantized_src1(st, b, a->type, ggml_abi_is_contiguous(b));
+                // (bytes: every head's matrix once per block of up to 8 columns)
+                timed_scope ts(c, (std::string("mmb_") + type_tag(a->type)).c_str(), (double) a->nb[2] * (double) (b->ne[2] * b->ne[3]) * (double) ((b->ne[1] + 7) / 8));
+                launch_mmb(s, m);
+                c->st.kernel_launches++;
+                return 1;
+            }
+            if (is_quant(a->type) && (a->ne[2] != 1 || a->ne[3] != 1)) {  // (the arms below are 2-D: e.g. a batch probed as a plain tensor and then placed outside a WEIGHTS buffer)
+                MI_ERR("graph_compute: node %d '%s': a batch of quantised matrices the backend does not serve (supports_op answers false for it)", i, n->name);
+                return -1;
             }
             if (!is_quant(a->type) && fuse && c->opt.attn_nf && try_fuse_attn_nf(st, i)) return 1;
             if (!is_quant(a->type) && fuse && c->opt.attn_nf && try_fuse_attn_nf_mma(st, i)) return 1;

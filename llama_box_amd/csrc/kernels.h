@@ -118,6 +118,19 @@ struct mmid_args {
 };
 void launch_mmid(hipStream_t s, const mmid_args & a);
 
+// ---- batched MUL_MAT over a 3-D quantised weight, one matrix per head: the absorbed MLA matrices of the deepseek2 graph (mmb.hip)
+struct mmb_args {
+    const uint8_t * W;     // a [K, N, H]: row stride w_nb1, matrix stride w_nb2 (bytes)
+    int64_t w_nb1, w_nb2;
+    int type;              // ggml_type of a: Q8_0, Q4_0, Q4_1, Q5_0, Q5_1, IQ4_NL, Q4_K, Q5_K, Q6_K
+    int K, N;
+    int M, Hb, E;          // b [K, M, Hb, E]; head hb reads matrix hb / r2
+    int r2;                // Hb / H
+    const void * act;      // b quantised: Q8_K / Q8_0 / Q8_1 blocks [E][Hb][M][K / blk] (launch_quantize_act of b)
+    float * dst;           // [N, M, Hb, E] contiguous
+};
+void launch_mmb(hipStream_t s, const mmb_args & a);
+
 // ---- fused Q/K/V projection for one token (qkv.hip): up to three K-quant mat-vecs that share their input, with the
 // activation prologue of mmvq (f32 or RMS_NORM*w), optional bias, rotary embedding and the KV-cache store in the epilogue
 struct qkv_seg {
@@ -440,6 +453,7 @@ void tu_touch_tp_p2p(hipStream_t s);
 void tu_touch_kv_types(hipStream_t s);
 void tu_touch_repack(hipStream_t s);
 void tu_touch_mmid(hipStream_t s);
+void tu_touch_mmb(hipStream_t s);
 void tu_touch_ssm(hipStream_t s);
 inline void preload_kernel_files(hipStream_t s) {
     tu_touch_kv_types(s);
@@ -447,6 +461,7 @@ inline void preload_kernel_files(hipStream_t s) {
     tu_touch_quantize(s);
     tu_touch_mmvq(s);
     tu_touch_mmid(s);
+    tu_touch_mmb(s);
     tu_touch_qkv(s);
     tu_touch_mmf(s);
     tu_touch_mmbf(s);
