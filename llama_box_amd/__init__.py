@@ -134,6 +134,9 @@ _SIGS = {
     "ggml_argsort": (TP, [_P, TP, _I]), "ggml_top_k": (TP, [_P, TP, _I]), "ggml_sum_rows": (TP, [_P, TP]), "ggml_clamp": (TP, [_P, TP, _F, _F]),
     "ggml_mul_mat_id": (TP, [_P, TP, TP, TP]),
     "ggml_concat": (TP, [_P, TP, TP, _I]), "ggml_ssm_conv": (TP, [_P, TP, TP]), "ggml_ssm_scan": (TP, [_P, TP, TP, TP, TP, TP, TP, TP]),
+    "ggml_sqr": (TP, [_P, TP]), "ggml_repeat": (TP, [_P, TP, TP]), "ggml_l2_norm": (TP, [_P, TP, _F]),
+    "ggml_rwkv_wkv6": (TP, [_P, TP, TP, TP, TP, TP, TP]), "ggml_rwkv_wkv7": (TP, [_P, TP, TP, TP, TP, TP, TP, TP]),
+    "ggml_gated_linear_attn": (TP, [_P, TP, TP, TP, TP, TP, _F]),
     "ggml_new_graph": (C.POINTER(CGraph), [_P]), "ggml_new_graph_custom": (C.POINTER(CGraph), [_P, _SZ, _B]),
     "ggml_build_forward_expand": (None, [C.POINTER(CGraph), TP]), "ggml_graph_n_nodes": (_I, [C.POINTER(CGraph)]),
     "ggml_graph_node": (TP, [C.POINTER(CGraph), _I]), "ggml_graph_view": (CGraph, [C.POINTER(CGraph), _I, _I]),

@@ -323,6 +323,44 @@ static bool ssm_scan_ok(const ggml_tensor * op) {
     return ggml_abi_nelements(op) == ggml_abi_nelements(x) + d_state * head_dim * n_head * n_s && op->ne[0] == ggml_abi_nelements(op);
 }
 
+// The ops of a linear-attention recurrent layer (rwkv.hip; DESIGN.md §4k restates their contracts).  Shapes, types and strides only.
+// RWKV_WKV6: src = {k, v, r, tf, td, state}; GATED_LINEAR_ATTN: {k, v, q, g, state}; RWKV_WKV7: {r, w, k, v, a, b, state}.  Everything f32 and contiguous; the
+// per-token operands [S, H, T, 1] with S 64 or 128, tf S * H elements, the state exactly S * S * H elements for each of its state->ne[1] sequences, T a whole
+// multiple of them; dst [S * H, T + S * n_seqs]: y, then the new states
+static bool rwkv_wkv_ok(const ggml_tensor * op) {
+    const int n_tok = op->op == GGML_OP_RWKV_WKV6 ? 5 : op->op == GGML_OP_GATED_LINEAR_ATTN ? 4 : op->op == GGML_OP_RWKV_WKV7 ? 6 : -1;
+    if (n_tok < 0) return false;
+    const ggml_tensor * x = op->src[0], * state = op->src[n_tok];
+    if (!x || !state || !is_f32_contig(state) || !is_f32_contig(op)) return false;
+    const int64_t S = x->ne[0], H = x->ne[1], T = x->ne[2], n_seqs = state->ne[1];
+    if ((S != 64 && S != 128) || H < 1 || T < 1 || n_seqs < 1 || T % n_seqs != 0) return false;
+    for (int i = 0; i < n_tok; ++i) {
+        const ggml_tensor * t = op->src[i];
+        if (!t || !is_f32_contig(t)) return false;
+        if (op->op == GGML_OP_RWKV_WKV6 && i == 3) {  // tf: one value per head and row
+            if (ggml_abi_nelements(t) != S * H) return false;
+            continue;
+        }
+        if (t->ne[0] != S || t->ne[1] != H || t->ne[2] != T || t->ne[3] != 1) return false;
+    }
+    if (n_seqs > 65535 || T > INT32_MAX / 2 || H > INT32_MAX / 512) return false;  // (grid.y; the kernels' int token counts; grid.x = H * S / 16)
+    if (ggml_abi_nelements(state) != S * S * H * n_seqs) return false;
+    return op->ne[0] == S * H && op->ne[1] == T + S * n_seqs && op->ne[2] == 1 && op->ne[3] == 1;
+}
+// L2_NORM: the NORM arm's condition and a row of at least one element
+static bool l2_norm_ok(const ggml_tensor * op) {
+    const ggml_tensor * a = op->src[0];
+    return a && a->type == GGML_TYPE_F32 && op->type == GGML_TYPE_F32 && a->nb[0] == 4 && op->nb[0] == 4 && a->ne[0] >= 1 && same_shape(a, op);
+}
+// REPEAT: f32, the result contiguous, the source at any element-aligned strides, every extent of the result a whole multiple of the source's
+static bool repeat_ok(const ggml_tensor * op) {
+    const ggml_tensor * a = op->src[0];
+    if (!a || a->type != GGML_TYPE_F32 || !is_f32_contig(op)) return false;
+    for (int d = 0; d < 4; ++d)
+        if (a->ne[d] < 1 || op->ne[d] % a->ne[d] != 0 || (a->nb[d] % 4)) return false;
+    return true;
+}
+
 bool supports_op(const ggml_tensor * op) {
     const ggml_tensor * a = op->src[0];
     const ggml_tensor * b = op->src[1];
@@ -419,6 +457,14 @@ bool supports_op(const ggml_tensor * op) {
             return ssm_conv_ok(op);
         case GGML_OP_SSM_SCAN:
             return ssm_scan_ok(op);
+        case GGML_OP_RWKV_WKV6: case GGML_OP_GATED_LINEAR_ATTN: case GGML_OP_RWKV_WKV7:
+            return rwkv_wkv_ok(op);
+        case GGML_OP_L2_NORM:
+            return l2_norm_ok(op);
+        case GGML_OP_SQR:
+            return is_f32_contig(a) && is_f32_contig(op);
+        case GGML_OP_REPEAT:
+            return repeat_ok(op);
         default:
             return false;
     }
@@ -2612,6 +2658,33 @@ static int run_node(exec_state & st, int i) {
             c->st.kernel_launches++;
             return 1;
         }
+        case GGML_OP_RWKV_WKV6: case GGML_OP_GATED_LINEAR_ATTN: case GGML_OP_RWKV_WKV7: {
+            if (!rwkv_wkv_ok(n)) { MI_ERR("graph_compute: node %d '%s' is outside the recurrent ops' contract (DESIGN.md 4k)", i, n->name); return -1; }
+            // (bytes: the states read and written; the per-token operands and y are small beside them at decode)
+            timed_scope ts(c, n->op == GGML_OP_RWKV_WKV6 ? "rwkv_wkv6" : n->op == GGML_OP_RWKV_WKV7 ? "rwkv_wkv7" : "gated_linear_attn", (double) (ggml_abi_nelements(n) - ggml_abi_nelements(a)) * 8);
+            const ggml_tensor * const * r = n->src;
+            bool ok;
+            if (n->op == GGML_OP_RWKV_WKV6) ok = launch_rwkv_wkv6(s, TD(r[0]), TD(r[1]), TD(r[2]), TD(r[3]), TD(r[4]), TD(r[5]), TD(n));
+            else if (n->op == GGML_OP_RWKV_WKV7) ok = launch_rwkv_wkv7(s, TD(r[0]), TD(r[1]), TD(r[2]), TD(r[3]), TD(r[4]), TD(r[5]), TD(r[6]), TD(n));
+            else ok = launch_gated_linear_attn(s, TD(r[0]), TD(r[1]), TD(r[2]), TD(r[3]), TD(r[4]), TD(n), ggml_abi_op_param_f32(n, 0));
+            if (!ok) return -1;
+            c->st.kernel_launches++;
+            return 1;
+        }
+        case GGML_OP_L2_NORM: {
+            timed_scope ts(c, "l2_norm", (double) ggml_abi_nbytes(n) * 2);
+            launch_l2_norm(s, TD(a), TD(n), ggml_abi_op_param_f32(n, 0));
+            c->st.kernel_launches++;
+            return 1;
+        }
+        case GGML_OP_SQR:
+            launch_sqr(s, TD(a), TD(n));
+            c->st.kernel_launches++;
+            return 1;
+        case GGML_OP_REPEAT:
+            launch_repeat(s, TD(a), TD(n));
+            c->st.kernel_launches++;
+            return 1;
         default:
             MI_ERR("graph_compute: unsupported op %d (node %d '%s')", (int) n->op, i, n->name);
             return -1;

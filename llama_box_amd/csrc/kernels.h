@@ -429,6 +429,16 @@ bool launch_ssm_conv(hipStream_t s, const tdesc & sx, const tdesc & c, const tde
 // SSM_SCAN, d_state 16 / 64 / 128 / 256, n_group 1 or n_head; dst: y, then the final states in sequence order
 bool launch_ssm_scan(hipStream_t s, const tdesc & st, const tdesc & x, const tdesc & dt, const tdesc & A, const tdesc & B, const tdesc & C, const tdesc & ids, const tdesc & dst);
 
+// ---- linear-attention recurrent layers (rwkv.hip): f32, head size 64 / 128, per-token operands [S, H, T] contiguous, the state S * S * H floats a
+// sequence, dst = y [S * H, T] then the new states.  The three recurrences return false at a shape supports_op refuses (graph.cpp: rwkv_wkv_ok)
+bool launch_rwkv_wkv6(hipStream_t s, const tdesc & k, const tdesc & v, const tdesc & r, const tdesc & tf, const tdesc & td, const tdesc & state, const tdesc & dst);
+bool launch_gated_linear_attn(hipStream_t s, const tdesc & k, const tdesc & v, const tdesc & q, const tdesc & g, const tdesc & state, const tdesc & dst, float scale);
+bool launch_rwkv_wkv7(hipStream_t s, const tdesc & r, const tdesc & w, const tdesc & k, const tdesc & v, const tdesc & a, const tdesc & b, const tdesc & state, const tdesc & dst);
+// L2_NORM: y = x / max(sqrt(sum x^2), eps) per row, rows at any strides (nb0 = 4); SQR: contiguous; REPEAT: dst contiguous, src with any element-aligned strides
+void launch_l2_norm(hipStream_t s, const tdesc & src, const tdesc & dst, float eps);
+void launch_sqr(hipStream_t s, const tdesc & src, const tdesc & dst);
+void launch_repeat(hipStream_t s, const tdesc & src, const tdesc & dst);
+
 // ---- code-object preload (round 4).  The HIP runtime loads a translation unit's device code on the FIRST launch of one of its kernels
 // (0.3 - 2 ms each, measured as idle gaps in front of the first prompt's kernels: 5.5 ms of a 64 ms prefill).  Every kernel file ends with
 // MI_TU_TOUCH(name): an empty kernel + a launcher; init_backend launches them all once per device, so the cost moves to start-up.
@@ -455,6 +465,7 @@ void tu_touch_repack(hipStream_t s);
 void tu_touch_mmid(hipStream_t s);
 void tu_touch_mmb(hipStream_t s);
 void tu_touch_ssm(hipStream_t s);
+void tu_touch_rwkv(hipStream_t s);
 inline void preload_kernel_files(hipStream_t s) {
     tu_touch_kv_types(s);
     tu_touch_repack(s);
@@ -476,6 +487,7 @@ inline void preload_kernel_files(hipStream_t s) {
     tu_touch_fattn_mma(s);
     tu_touch_tp_p2p(s);
     tu_touch_ssm(s);
+    tu_touch_rwkv(s);
 }
 
 }  // namespace mi355x

@@ -757,6 +757,8 @@ static bool analyse_node(analysis & A, const ggml_tensor * t) {
         }
         case GGML_OP_GET_ROWS: case GGML_OP_RMS_NORM: case GGML_OP_SCALE: case GGML_OP_UNARY: case GGML_OP_CPY: case GGML_OP_DUP: case GGML_OP_ARGMAX:
             return all_replicated();
+        case GGML_OP_RWKV_WKV6: case GGML_OP_GATED_LINEAR_ATTN: case GGML_OP_RWKV_WKV7: case GGML_OP_L2_NORM: case GGML_OP_SQR: case GGML_OP_REPEAT:
+            return A.fail("an op of a linear-attention recurrent layer, which the engine has no rule for", t);  // (as it has none for the SSM ops)
         default:
             return A.fail("an op the engine has no rule for", t);
     }

@@ -648,6 +648,69 @@ struct ggml_tensor * ggml_ssm_scan(struct ggml_context * ctx, struct ggml_tensor
     return r;
 }
 
+// linear-attention recurrent layers (llama.cpp build_rwkv6_time_mix / build_rwkv7_time_mix / the channel mixes; DESIGN.md §4k states the contracts)
+struct ggml_tensor * ggml_sqr(struct ggml_context * ctx, struct ggml_tensor * a) {
+    ggml_tensor * r = dup_tensor(ctx, a);
+    r->op = GGML_OP_SQR;
+    r->src[0] = a;
+    return r;
+}
+struct ggml_tensor * ggml_repeat(struct ggml_context * ctx, struct ggml_tensor * a, struct ggml_tensor * b) {
+    LITE_ASSERT(can_repeat(a, b));
+    ggml_tensor * r = ggml_new_tensor(ctx, a->type, GGML_MAX_DIMS, b->ne);
+    r->op = GGML_OP_REPEAT;
+    r->src[0] = a;
+    return r;
+}
+struct ggml_tensor * ggml_l2_norm(struct ggml_context * ctx, struct ggml_tensor * a, float eps) {
+    ggml_tensor * r = dup_tensor(ctx, a);
+    set_f32(r, 0, eps);
+    r->op = GGML_OP_L2_NORM;
+    r->src[0] = a;
+    return r;
+}
+// the result of the three recurrences: y [S * H, n_tokens], then the new states [S * H, S * n_seqs], as one matrix
+static ggml_tensor * wkv_result(ggml_context * ctx, ggml_op op, ggml_tensor * const * src, int n_src) {
+    const ggml_tensor * x = src[0], * state = src[n_src - 1];
+    const int64_t S = x->ne[0], H = x->ne[1], n_tokens = x->ne[2], n_seqs = state->ne[1];
+    LITE_ASSERT(ggml_nelements(state) == S * S * H * n_seqs);
+    ggml_tensor * r = ggml_new_tensor_4d(ctx, GGML_TYPE_F32, S * H, n_tokens + S * n_seqs, 1, 1);
+    r->op = op;
+    for (int i = 0; i < n_src; ++i) r->src[i] = src[i];
+    return r;
+}
+struct ggml_tensor * ggml_rwkv_wkv6(struct ggml_context * ctx, struct ggml_tensor * k, struct ggml_tensor * v, struct ggml_tensor * r, struct ggml_tensor * tf,
+                                    struct ggml_tensor * td, struct ggml_tensor * state) {
+    LITE_ASSERT(ggml_is_contiguous(k) && ggml_is_contiguous(v) && ggml_is_contiguous(r) && ggml_is_contiguous(tf) && ggml_is_contiguous(td) && ggml_is_contiguous(state));
+    const int64_t S = k->ne[0], H = k->ne[1], n_tokens = k->ne[2];
+    LITE_ASSERT(v->ne[0] == S && v->ne[1] == H && v->ne[2] == n_tokens);
+    LITE_ASSERT(r->ne[0] == S && r->ne[1] == H && r->ne[2] == n_tokens);
+    LITE_ASSERT(td->ne[0] == S && td->ne[1] == H && td->ne[2] == n_tokens);
+    ggml_tensor * src[6] = {k, v, r, tf, td, state};
+    return wkv_result(ctx, GGML_OP_RWKV_WKV6, src, 6);
+}
+struct ggml_tensor * ggml_gated_linear_attn(struct ggml_context * ctx, struct ggml_tensor * k, struct ggml_tensor * v, struct ggml_tensor * q, struct ggml_tensor * g,
+                                            struct ggml_tensor * state, float scale) {
+    LITE_ASSERT(ggml_is_contiguous(k) && ggml_is_contiguous(v) && ggml_is_contiguous(q) && ggml_is_contiguous(g) && ggml_is_contiguous(state));
+    const int64_t S = k->ne[0], H = k->ne[1], n_tokens = k->ne[2];
+    LITE_ASSERT(v->ne[0] == S && v->ne[1] == H && v->ne[2] == n_tokens);
+    LITE_ASSERT(q->ne[0] == S && q->ne[1] == H && q->ne[2] == n_tokens);
+    LITE_ASSERT(g->ne[0] == S && g->ne[1] == H && g->ne[2] == n_tokens);
+    ggml_tensor * src[5] = {k, v, q, g, state};
+    ggml_tensor * res = wkv_result(ctx, GGML_OP_GATED_LINEAR_ATTN, src, 5);
+    set_f32(res, 0, scale);
+    return res;
+}
+struct ggml_tensor * ggml_rwkv_wkv7(struct ggml_context * ctx, struct ggml_tensor * r, struct ggml_tensor * w, struct ggml_tensor * k, struct ggml_tensor * v,
+                                    struct ggml_tensor * a, struct ggml_tensor * b, struct ggml_tensor * state) {
+    LITE_ASSERT(ggml_is_contiguous(r) && ggml_is_contiguous(w) && ggml_is_contiguous(k) && ggml_is_contiguous(v) && ggml_is_contiguous(a) && ggml_is_contiguous(b) &&
+                ggml_is_contiguous(state));
+    const int64_t S = k->ne[0], H = k->ne[1], n_tokens = k->ne[2];
+    for (const ggml_tensor * t : {r, w, v, a, b}) LITE_ASSERT(t->ne[0] == S && t->ne[1] == H && t->ne[2] == n_tokens);
+    ggml_tensor * src[7] = {r, w, k, v, a, b, state};
+    return wkv_result(ctx, GGML_OP_RWKV_WKV7, src, 7);
+}
+
 // ------------------------------------------------------------------------------------------------ graphs
 struct ggml_cgraph * ggml_new_graph_custom(struct ggml_context * ctx, size_t size, bool) {
     ggml_cgraph * g = new ggml_cgraph();

@@ -135,6 +135,18 @@ struct ggml_tensor * ggml_ssm_conv(struct ggml_context * ctx, struct ggml_tensor
  * ids i32 [n_s] -> one f32 vector: y [head_dim, n_head, n_t, n_s], then the final states [d_state, head_dim, n_head, n_s] */
 struct ggml_tensor * ggml_ssm_scan(struct ggml_context * ctx, struct ggml_tensor * s, struct ggml_tensor * x, struct ggml_tensor * dt, struct ggml_tensor * A,
                                    struct ggml_tensor * B, struct ggml_tensor * C, struct ggml_tensor * ids);
+/* linear-attention recurrent layers (llama.cpp rwkv6 / rwkv6qwen2 / rwkv7 / arwkv7; DESIGN.md §4k states the contracts) */
+struct ggml_tensor * ggml_sqr(struct ggml_context * ctx, struct ggml_tensor * a);
+struct ggml_tensor * ggml_repeat(struct ggml_context * ctx, struct ggml_tensor * a, struct ggml_tensor * b);  /* a repeated to b's shape */
+struct ggml_tensor * ggml_l2_norm(struct ggml_context * ctx, struct ggml_tensor * a, float eps);
+/* k, v, r, td (and q, g, w, a, b) [S, H, n_tokens], tf [S, H], state S * S * H floats for each of its ne[1] sequences -> [S * H, n_tokens + S * n_seqs]:
+ * y [S * H, n_tokens], then the new states */
+struct ggml_tensor * ggml_rwkv_wkv6(struct ggml_context * ctx, struct ggml_tensor * k, struct ggml_tensor * v, struct ggml_tensor * r, struct ggml_tensor * tf,
+                                    struct ggml_tensor * td, struct ggml_tensor * state);
+struct ggml_tensor * ggml_rwkv_wkv7(struct ggml_context * ctx, struct ggml_tensor * r, struct ggml_tensor * w, struct ggml_tensor * k, struct ggml_tensor * v,
+                                    struct ggml_tensor * a, struct ggml_tensor * b, struct ggml_tensor * state);
+struct ggml_tensor * ggml_gated_linear_attn(struct ggml_context * ctx, struct ggml_tensor * k, struct ggml_tensor * v, struct ggml_tensor * q, struct ggml_tensor * g,
+                                            struct ggml_tensor * state, float scale);
 
 /* graphs */
 struct ggml_cgraph * ggml_new_graph(struct ggml_context * ctx);
