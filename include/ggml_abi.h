@@ -487,7 +487,7 @@ static_assert(sizeof(struct ggml_tensor) % GGML_MEM_ALIGN == 0, "ggml_tensor ali
 /* ------- small inline helpers every side needs (own implementations, not ggml's code) ------- */
 static inline int64_t ggml_abi_blck_size(enum ggml_type t) {
     switch (t) {
-        case GGML_TYPE_Q8_0: case GGML_TYPE_Q4_0: case GGML_TYPE_Q4_1: case GGML_TYPE_Q5_0: case GGML_TYPE_Q5_1: case GGML_TYPE_Q8_1: case GGML_TYPE_IQ4_NL: return 32;
+        case GGML_TYPE_Q8_0: case GGML_TYPE_Q4_0: case GGML_TYPE_Q4_1: case GGML_TYPE_Q5_0: case GGML_TYPE_Q5_1: case GGML_TYPE_Q8_1: case GGML_TYPE_IQ4_NL: case GGML_TYPE_MXFP4: return 32;
         case GGML_TYPE_Q2_K: case GGML_TYPE_Q3_K: case GGML_TYPE_Q4_K: case GGML_TYPE_Q5_K: case GGML_TYPE_Q6_K: case GGML_TYPE_Q8_K: case GGML_TYPE_IQ4_XS: return 256;
         default: return 1;
     }
@@ -500,6 +500,7 @@ static inline size_t ggml_abi_type_size(enum ggml_type t) {
         case GGML_TYPE_I64: case GGML_TYPE_F64: return 8;
         case GGML_TYPE_Q8_0: return 34;
         case GGML_TYPE_Q4_0: case GGML_TYPE_IQ4_NL: return 18;
+        case GGML_TYPE_MXFP4: return 17;  /* block_mxfp4: u8 e | u8 qs[16] */
         case GGML_TYPE_Q4_1: return 20;
         case GGML_TYPE_Q5_0: return 22;
         case GGML_TYPE_Q5_1: return 24;

@@ -26,10 +26,11 @@ HOST_SO = os.path.join(_DIR, "libmi355x_host.so")
 F32, F16, Q8_0, Q4_K, Q5_K, Q6_K, Q8_K, I32, I64 = 0, 1, 8, 12, 13, 14, 15, 26, 27
 Q4_0, Q4_1, Q5_0, Q5_1, Q8_1, IQ4_NL, BF16 = 2, 3, 6, 7, 9, 20, 30  # the other types a KV cache may be kept in (-ctk / -ctv) and the Q8_1 activation block
 Q2_K, Q3_K = 10, 11  # the two smallest K-quants: 16 sub-blocks of 16 values, 84 / 110 bytes per 256 values
+MXFP4 = 39  # gpt-oss expert matrices: 32 E2M1 values under one E8M0 scale, 17 bytes per 32 values
 IQ4_XS = 23  # IQ4_NL's table under a K-quant frame: 8 sub-blocks of 32 values with six-bit scales, 136 bytes per 256 values
-TYPE_BLCK = {IQ4_XS: 256, Q2_K: 256, Q3_K: 256, F32: 1, F16: 1, Q8_0: 32, Q4_K: 256, Q5_K: 256, Q6_K: 256, Q8_K: 256, I32: 1, I64: 1, Q4_0: 32, Q4_1: 32, Q5_0: 32, Q5_1: 32, Q8_1: 32, IQ4_NL: 32, BF16: 1}
-TYPE_SIZE = {IQ4_XS: 136, Q2_K: 84, Q3_K: 110, F32: 4, F16: 2, Q8_0: 34, Q4_K: 144, Q5_K: 176, Q6_K: 210, Q8_K: 292, I32: 4, I64: 8, Q4_0: 18, Q4_1: 20, Q5_0: 22, Q5_1: 24, Q8_1: 36, IQ4_NL: 18, BF16: 2}
-TYPE_NAME = {F32: "f32", F16: "f16", BF16: "bf16", Q8_0: "q8_0", Q4_0: "q4_0", Q4_1: "q4_1", Q5_0: "q5_0", Q5_1: "q5_1", IQ4_NL: "iq4_nl", Q2_K: "q2_K", Q3_K: "q3_K", IQ4_XS: "iq4_xs"}
+TYPE_BLCK = {MXFP4: 32, IQ4_XS: 256, Q2_K: 256, Q3_K: 256, F32: 1, F16: 1, Q8_0: 32, Q4_K: 256, Q5_K: 256, Q6_K: 256, Q8_K: 256, I32: 1, I64: 1, Q4_0: 32, Q4_1: 32, Q5_0: 32, Q5_1: 32, Q8_1: 32, IQ4_NL: 32, BF16: 1}
+TYPE_SIZE = {MXFP4: 17, IQ4_XS: 136, Q2_K: 84, Q3_K: 110, F32: 4, F16: 2, Q8_0: 34, Q4_K: 144, Q5_K: 176, Q6_K: 210, Q8_K: 292, I32: 4, I64: 8, Q4_0: 18, Q4_1: 20, Q5_0: 22, Q5_1: 24, Q8_1: 36, IQ4_NL: 18, BF16: 2}
+TYPE_NAME = {F32: "f32", F16: "f16", BF16: "bf16", Q8_0: "q8_0", Q4_0: "q4_0", Q4_1: "q4_1", Q5_0: "q5_0", Q5_1: "q5_1", IQ4_NL: "iq4_nl", Q2_K: "q2_K", Q3_K: "q3_K", IQ4_XS: "iq4_xs", MXFP4: "mxfp4"}
 LLM_FTYPE_BF16 = 16  # host/llama_lite.h: every matrix, token_embd and output in bf16
 GGML_MAX_NAME = 128
 ROPE_NEOX = 2
@@ -132,7 +133,7 @@ _SIGS = {
     "ggml_flash_attn_ext": (TP, [_P, TP, TP, TP, TP, _F, _F, _F]), "ggml_flash_attn_ext_set_prec": (None, [TP, _I]),
     "ggml_flash_attn_ext_add_sinks": (None, [TP, TP]), "ggml_argmax": (TP, [_P, TP]),
     "ggml_argsort": (TP, [_P, TP, _I]), "ggml_top_k": (TP, [_P, TP, _I]), "ggml_sum_rows": (TP, [_P, TP]), "ggml_clamp": (TP, [_P, TP, _F, _F]),
-    "ggml_mul_mat_id": (TP, [_P, TP, TP, TP]),
+    "ggml_mul_mat_id": (TP, [_P, TP, TP, TP]), "ggml_add_id": (TP, [_P, TP, TP, TP]), "ggml_swiglu_oai": (TP, [_P, TP, TP, _F, _F]),
     "ggml_concat": (TP, [_P, TP, TP, _I]), "ggml_ssm_conv": (TP, [_P, TP, TP]), "ggml_ssm_scan": (TP, [_P, TP, TP, TP, TP, TP, TP, TP]),
     "ggml_sqr": (TP, [_P, TP]), "ggml_repeat": (TP, [_P, TP, TP]), "ggml_l2_norm": (TP, [_P, TP, _F]),
     "ggml_rwkv_wkv6": (TP, [_P, TP, TP, TP, TP, TP, TP]), "ggml_rwkv_wkv7": (TP, [_P, TP, TP, TP, TP, TP, TP, TP]),

@@ -725,6 +725,7 @@ static ggml_backend_t dev_init_backend(ggml_backend_dev_t dev, const char *) {
     }
     options_from_env(c->opt);
     c->ssm_fuse = env_flag("GGML_MI355X_SSM_FUSE", true);
+    c->mmid_bias = env_flag("GGML_MI355X_MMID_BIAS", true);
     if (hipMalloc((void **) &c->ss_buf, 256 * sizeof(double)) != hipSuccess) {  // (optional: without it every norm prologue sums its own row)
         (void) hipGetLastError();
         c->ss_buf = nullptr;
@@ -828,6 +829,7 @@ static int api_set_option(ggml_backend_t be, const char * key, const char * valu
         else if (k == "clear_failure") { if (v) clear_hip_failure(); }
         else if (k == "staged_upload") g_staged_upload.store(v != 0);
         else if (k == "ssm_fuse") c->ssm_fuse = v != 0;
+        else if (k == "mmid_bias") c->mmid_bias = v != 0;
         else return -1;
     }
     HIP_SOFT(hipStreamSynchronize(c->stream));

@@ -100,6 +100,18 @@ __device__ __forceinline__ uint32_t iq4nl_bytes(const uint32_t n) {
     const uint32_t s = n & 0x07070707u, m = ((n >> 3) & 0x01010101u) * 0xFFu;
     return (__builtin_amdgcn_perm(A1, A0, s) & ~m) | (__builtin_amdgcn_perm(B1, B0, s) & m);
 }
+// MXFP4 (ggml's block_mxfp4): the E8M0 block scale halved, as f32 bits (e < 2: the two subnormal powers 2^-128 and 2^-127), and the table
+// {0, 1, 2, 3 | 4, 6, 8, 12 || 0, -1, -2, -3 | -4, -6, -8, -12} applied to the four codes (0 .. 15, one a byte) of a dword: bit 3 picks the signed half
+__host__ __device__ __forceinline__ uint32_t mxfp4_scale_bits(const uint32_t e) { return e < 2u ? 0x00200000u << e : (e - 1u) << 23; }
+__device__ __forceinline__ uint32_t mxfp4_bytes(const uint32_t n) {
+    constexpr uint32_t A0 = 0x03020100u, A1 = 0x0C080604u, B0 = 0xFDFEFF00u, B1 = 0xF4F8FAFCu;
+    const uint32_t sel = n & 0x07070707u, m = ((n >> 3) & 0x01010101u) * 0xFFu;
+    return (__builtin_amdgcn_perm(A1, A0, sel) & ~m) | (__builtin_amdgcn_perm(B1, B0, sel) & m);
+}
+__device__ __forceinline__ float mxfp4_value(const uint32_t n) {  // one code as f32 (GET_ROWS)
+    const int mag = (int) ((0x0C08060403020100ull >> (8 * (n & 7u))) & 0xFFu);
+    return (float) ((n & 8u) ? -mag : mag);  // (code 8 is +0.0, as the reference's integer table gives)
+}
 
 __device__ __forceinline__ float silu_f(float x) { return x / (1.0f + expf(-x)); }
 

@@ -18,6 +18,7 @@ namespace mi355x {
 
 static bool is_kq23_type(int t) { return t == GGML_TYPE_Q2_K || t == GGML_TYPE_Q3_K; }
 static bool is_iq4xs_type(int t) { return t == GGML_TYPE_IQ4_XS; }
+static bool is_mxfp4_type(int t) { return t == GGML_TYPE_MXFP4; }
 // what this file knows of a quantised weight type, one row per type: a new format is a new row here (and its hand-over in mmq_min_cols_for)
 struct wtype_info {
     int type;
@@ -39,6 +40,8 @@ static const wtype_info k_wtypes[] = {
     {GGML_TYPE_Q2_K, "q2_K", GGML_TYPE_Q8_K, 4, true},
     {GGML_TYPE_Q3_K, "q3_K", GGML_TYPE_Q8_K, 2, true},
     {GGML_TYPE_IQ4_XS, "iq4_xs", GGML_TYPE_Q8_K, 8, true},
+    // (17-byte blocks start at any byte: the alignment of 1 is there only so that l32_layout_ok keeps the split and row-parallel buffer types refusing the format)
+    {GGML_TYPE_MXFP4, "mxfp4", GGML_TYPE_Q8_0, 1, false},
 };
 static const wtype_info * wtype_row(int t) {
     for (const wtype_info & r : k_wtypes)
@@ -87,6 +90,9 @@ static inline int mmq_min_cols_for(const backend_ctx * c, int wtype) {
     // The hand-over was set where the one-pass form ends and not compared with other thresholds.
     // IQ4_XS: the same hand-over, taken from Q2_K / Q3_K and not compared with other thresholds either.
     if (is_kq23_type(wtype) || is_iq4xs_type(wtype)) return 9;
+    // MXFP4: never — no matrix-core form reads the format (mmq_q80.hip's staging carries the block scale as f16, which an E8M0 scale does not fit), so batch_form
+    // answers MM_VEC for every M and plan_ws sizes no split-K area for it
+    if (is_mxfp4_type(wtype)) return INT32_MAX;
     if (c->opt.mmq_min_cols != 3) return c->opt.mmq_min_cols;
     return (wtype == GGML_TYPE_Q4_K || (wtype == GGML_TYPE_Q6_K && !c->mm_q5_major)) ? 2 : 3;
 }
@@ -181,7 +187,8 @@ static bool mm_runs_on_image(const ggml_tensor * n) { return mm_cache_image_ok(n
 //     loader probes (what mm_cache_image_ok takes is excluded here: a block-format batch outside a weights buffer is a KV-cache view and keeps its f16 image);
 //   b [K, M, H * r2, E] f32, rows contiguous, dims 1 .. 3 at any element-aligned stride (ggml_permute(q_nope, 0, 2, 1, 3) of a strided view: nb[1] > nb[2]);
 //   dst [N, M, H * r2, E] f32 contiguous:  dst(:, m, h, e) = a(:, :, h / r2) · q(b(:, m, h, e))
-// Q2_K / Q3_K / IQ4_XS (and bf16) batches stay refused: their 2-D acceptance was merged with tests that pin the 3-D refusal.  The split (-sm row) and row-parallel
+// Q2_K / Q3_K / IQ4_XS (and bf16) batches stay refused: their 2-D acceptance was merged with tests that pin the 3-D refusal.  MXFP4 batches too: launch_mmb has no
+// arm for the format (its 3-D tensors are expert matrices, read by MUL_MAT_ID).  The split (-sm row) and row-parallel
 // buffer types keep refusing.  The whole contract is here: supports_op, run_node, plan_ws and the in-process tensor-parallel engine (which declines) ask nobody else.
 bool mm_batched_q_ok(const ggml_tensor * op) {
     if (op->op != GGML_OP_MUL_MAT) return false;
@@ -193,7 +200,7 @@ bool mm_batched_q_ok(const ggml_tensor * op) {
     // broadcast, say — was refused and still is); no buffer at all is the loader's probe
     const ggml_backend_buffer_t root = a->view_src && a->view_src->buffer ? a->view_src->buffer : a->buffer;
     if (root && root->usage != GGML_BACKEND_BUFFER_USAGE_WEIGHTS) return false;
-    if (!is_quant(a->type) || is_kq23_type(a->type) || is_iq4xs_type(a->type)) return false;
+    if (!is_quant(a->type) || is_kq23_type(a->type) || is_iq4xs_type(a->type) || is_mxfp4_type(a->type)) return false;
     if (a->ne[2] < 2 || a->ne[3] != 1 || !rows_contig(a) || a->ne[0] < 1 || a->ne[1] < 1 || a->ne[0] % ggml_abi_blck_size(a->type) != 0) return false;
     if (needs_layout_check(a->type) && !l32_layout_ok(a)) return false;  // (the aligned formats: base, nb[1], nb[2] at the block alignment; not row-parallel, not split)
     if (weight_is_rowpar(a) || buffer_is_split(a->buffer)) return false;
@@ -266,6 +273,24 @@ static bool mm_id_ok(const ggml_tensor * op) {
     if (b->ne[1] != 1 && b->ne[1] != ids->ne[0]) return false;
     if (ids->ne[0] * ids->ne[1] > 65535 || a->ne[0] > INT32_MAX / 2 || a->ne[1] > INT32_MAX / 2 || a->ne[2] > INT32_MAX / 2) return false;
     return op->ne[0] == a->ne[1] && op->ne[1] == ids->ne[0] && op->ne[2] == ids->ne[1] && op->ne[3] == 1;
+}
+// ADD_ID (mmid.hip): a f32 [n, n_used, n_tokens] with contiguous rows at element-aligned strides; b f32 [n, n_expert] with contiguous rows; ids I32 [n_used, n_tokens],
+// possibly a strided view (mm_id_ok's conditions); dst f32 contiguous.  dst(:, s, t) = a(:, s, t) + b(:, ids(s, t)).  Shapes, types and strides only.
+static bool add_id_ok(const ggml_tensor * op) {
+    const ggml_tensor * a = op->src[0];
+    const ggml_tensor * b = op->src[1];
+    const ggml_tensor * ids = op->src[2];
+    if (!a || !b || !ids || a->type != GGML_TYPE_F32 || b->type != GGML_TYPE_F32 || ids->type != GGML_TYPE_I32 || !is_f32_contig(op) || !same_shape(a, op)) return false;
+    if (a->nb[0] != 4 || (a->nb[1] % 4) || (a->nb[2] % 4) || a->ne[3] != 1 || a->ne[0] < 1 || a->ne[1] < 1 || a->ne[2] < 1) return false;
+    if (b->nb[0] != 4 || (b->nb[1] % 4) || b->ne[0] != a->ne[0] || b->ne[1] < 1 || b->ne[2] != 1 || b->ne[3] != 1) return false;
+    if (ids->nb[0] != 4 || (ids->nb[1] % 4) || ids->ne[2] != 1 || ids->ne[3] != 1 || ids->ne[0] != a->ne[1] || ids->ne[1] != a->ne[2]) return false;
+    return a->ne[1] * a->ne[2] <= INT32_MAX / 2 && b->ne[1] <= INT32_MAX / 2;  // (grid x = pairs; int ids)
+}
+// SWIGLU_OAI's parameters (op_params[2..3] as f32): served when limit is finite and > 0 and alpha is finite.  With limit <= 0 the clamps leave nothing of the
+// operands and no model builds the node (gpt-oss: alpha 1.702, limit 7.0) — such a node stays refused, as every SWIGLU_OAI node was before the kernel existed.
+static bool swiglu_oai_params_ok(const ggml_tensor * op) {
+    const float alpha = ggml_abi_op_param_f32(op, 2), limit = ggml_abi_op_param_f32(op, 3);
+    return std::isfinite(alpha) && std::isfinite(limit) && limit > 0.0f;
 }
 // the 3-D split SwiGLU of an expert FFN ([n_ff, n_used, n_tokens]): rows one row stride apart through every dimension, so the row index is flat
 static bool glu_rows_dense(const ggml_tensor * t) { return t->nb[2] == t->nb[1] * (size_t) t->ne[1] && t->nb[3] == t->nb[2] * (size_t) t->ne[2]; }
@@ -389,6 +414,8 @@ bool supports_op(const ggml_tensor * op) {
         }
         case GGML_OP_MUL_MAT_ID:
             return mm_id_ok(op);
+        case GGML_OP_ADD_ID:
+            return add_id_ok(op);
         case GGML_OP_ARGSORT:
             return a->type == GGML_TYPE_F32 && a->nb[0] == 4 && a->ne[0] >= 1 && a->ne[0] <= MI_ARGSORT_MAX_COLS && op->type == GGML_TYPE_I32 && ggml_abi_is_contiguous(op) &&
                    (op->op_params[0] == 0 || op->op_params[0] == 1);  // GGML_SORT_ORDER_ASC / _DESC
@@ -408,8 +435,8 @@ bool supports_op(const ggml_tensor * op) {
                             u == GGML_UNARY_OP_TANH || u == GGML_UNARY_OP_SIGMOID || is_gelu_op(u);
             return ok && is_f32_contig(a) && is_f32_contig(op);
         }
-        case GGML_OP_GLU:  // (SWIGLU_OAI: refused)
-            return (op->op_params[0] == GGML_GLU_OP_SWIGLU || is_act_glu_op(op->op_params[0])) && a->type == GGML_TYPE_F32 && a->nb[0] == 4 && (!b || (b->type == GGML_TYPE_F32 && b->nb[0] == 4)) &&
+        case GGML_OP_GLU:  // (SWIGLU_OAI: only with the parameters a model builds — swiglu_oai_params_ok says why a node with limit <= 0 stays refused)
+            return (op->op_params[0] == GGML_GLU_OP_SWIGLU || is_act_glu_op(op->op_params[0]) || (op->op_params[0] == GGML_GLU_OP_SWIGLU_OAI && swiglu_oai_params_ok(op))) && a->type == GGML_TYPE_F32 && a->nb[0] == 4 && (!b || (b->type == GGML_TYPE_F32 && b->nb[0] == 4)) &&
                    ((a->ne[2] == 1 && a->ne[3] == 1) || (b && glu_rows_dense(a) && glu_rows_dense(b) && glu_rows_dense(op))) && op->nb[0] == 4;
         case GGML_OP_CPY: case GGML_OP_DUP: case GGML_OP_CONT: {
             const int st = a->type, dt = op->type;
@@ -421,6 +448,7 @@ bool supports_op(const ggml_tensor * op) {
             return (st == GGML_TYPE_F32 || st == GGML_TYPE_F16) && (dt == GGML_TYPE_F32 || dt == GGML_TYPE_F16);
         }
         case GGML_OP_GET_ROWS:
+            if (is_mxfp4_type(a->type) && a->ne[0] % 32 != 0) return false;  // (whole blocks a row, as the MUL_MAT arms ask)
             if (needs_layout_check(a->type) && !l32_layout_ok(a)) return false;  // (token_embd in q4_0 / q2_K / q3_K / iq4_xs ...: the block alignment and buffer types of the MUL_MAT arm)
             return b->type == GGML_TYPE_I32 && op->type == GGML_TYPE_F32 && rows_contig(a) && op->nb[0] == 4 &&
                    (is_quant(a->type) || a->type == GGML_TYPE_F16 || a->type == GGML_TYPE_BF16 || a->type == GGML_TYPE_F32);
@@ -2268,9 +2296,23 @@ static int run_node(exec_state & st, int i) {
             m.n_used = (int) ids->ne[0];
             m.n_tokens = (int) ids->ne[1];
             m.b_rows = (int) b->ne[1];
-            m.dst = (float *) n->data;
-            m.dst_nb1 = (int64_t) (n->nb[1] / 4);
-            m.dst_nb2 = (int64_t) (n->nb[2] / 4);
+            // MUL_MAT_ID -> ADD_ID (gpt-oss's per-expert bias): the ADD_ID directly behind this node, this result's only reader, over the same ids tensor, rides in
+            // the store.  The launch then writes the ADD_ID's block: not when that block is one a workgroup still reads (the bias, the ids, or b — the f16 / f32
+            // expert kernels read b itself while other workgroups store).  The quantised kernels read b's blocks in the activation area, not b, so for them an
+            // overlap with b alone would do no harm (run_nodes drops the activation cache's key for b when a node of this call writes into b's range); it is
+            // declined all the same, one rule for both kernel families, and nothing the allocator does to a gpt-oss graph meets it
+            ggml_tensor * n1 = next(1);
+            const bool bias = fuse && c->mmid_bias && n1 && n1->op == GGML_OP_ADD_ID && n1->src[0] == n && n1->src[2] == ids && single_use(st, n) && add_id_ok(n1) &&
+                              n1->src[1]->ne[1] == a->ne[2] && !ranges_overlap(n1, n1->src[1]) && !ranges_overlap(n1, ids) && !ranges_overlap(n1, b);
+            ggml_tensor * out = bias ? n1 : n;
+            if (bias) {
+                m.bias = (const char *) n1->src[1]->data;
+                m.bias_nb1 = (int64_t) n1->src[1]->nb[1];
+                if (st.ss_tensor != nullptr && ranges_overlap(n1, st.ss_tensor)) st.ss_tensor = nullptr;
+            }
+            m.dst = (float *) out->data;
+            m.dst_nb1 = (int64_t) (out->nb[1] / 4);
+            m.dst_nb2 = (int64_t) (out->nb[2] / 4);
             if (is_quant(a->type)) m.act = quantized_src1(st, b, a->type);
             else {
                 m.x = (const char *) b->data;
@@ -2282,6 +2324,20 @@ static int run_node(exec_state & st, int i) {
             launch_mmid(s, m);
             c->st.kernel_launches++;
             c->st.mmid_launches++;
+            if (bias) {
+                c->st.fused_nodes += 1;
+                return 2;
+            }
+            return 1;
+        }
+        case GGML_OP_ADD_ID: {
+            if (!add_id_ok(n)) {
+                MI_ERR("graph_compute: node %d '%s': ADD_ID operands the backend does not serve (supports_op answers false for them)", i, n->name);
+                return -1;
+            }
+            timed_scope ts(c, "add_id", (double) ggml_abi_nbytes(n) * 3);
+            launch_add_id(s, TD(a), TD(b), TD(n->src[2]), TD(n));
+            c->st.kernel_launches++;
             return 1;
         }
         case GGML_OP_ARGSORT:
@@ -2332,6 +2388,16 @@ static int run_node(exec_state & st, int i) {
                 mark_q8_cache(st, n, MI_ACT_Q80_PANEL);
                 c->st.kernel_launches++;
                 c->st.fused_nodes++;
+                return 1;
+            }
+            if (n->op_params[0] == GGML_GLU_OP_SWIGLU_OAI) {  // gpt-oss's gated unit (ops.hip, beside the expf it shares with the 3-D SwiGLU): no fused producer
+                if (!swiglu_oai_params_ok(n)) {
+                    MI_ERR("graph_compute: node %d '%s': SWIGLU_OAI parameters the backend does not serve (supports_op answers false for them)", i, n->name);
+                    return -1;
+                }
+                timed_scope ts(c, "swiglu_oai", (double) ggml_abi_nbytes(n) * 3);
+                launch_swiglu_oai(s, TD(a), b ? &bd : nullptr, TD(n), n->op_params[1], ggml_abi_op_param_f32(n, 2), ggml_abi_op_param_f32(n, 3));
+                c->st.kernel_launches++;
                 return 1;
             }
             if (!swiglu) {  // REGLU, GEGLU, GEGLU_QUICK, GEGLU_ERF (ops_act.hip): no fused producer yet

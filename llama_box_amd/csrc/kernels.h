@@ -104,7 +104,7 @@ extern thread_local launch_probe g_launch_probe;
 struct mmid_args {
     const uint8_t * W;     // `as` [K, N, n_expert]: row stride w_nb1, expert stride w_nb2 (bytes)
     int64_t w_nb1, w_nb2;
-    int type;              // ggml_type of `as`: Q4_K, Q5_K, Q6_K, Q8_0, F16, F32
+    int type;              // ggml_type of `as`: a mat-vec format (MXFP4 among them), F16, BF16, F32
     int K, N, n_expert;
     const char * ids;      // I32 [n_used, n_tokens], token stride ids_nb1 bytes (a view of ARGSORT's rows)
     int64_t ids_nb1;
@@ -115,8 +115,12 @@ struct mmid_args {
     int64_t x_nb1, x_nb2;
     float * dst;           // dst[token * dst_nb2 + slot * dst_nb1 + row]  (strides in elements)
     int64_t dst_nb1, dst_nb2;
+    const char * bias;     // ADD_ID in the store (null: none): f32 [N, n_expert], row stride bias_nb1 bytes; dst = acc + bias[id][row]
+    int64_t bias_nb1;
 };
 void launch_mmid(hipStream_t s, const mmid_args & a);
+// ADD_ID on its own: dst(:, s, t) = a(:, s, t) + b(:, ids(s, t)); a f32 [n, n_used, n_tokens] with contiguous rows, b f32 [n, n_expert], ids I32 (token stride nb[1])
+void launch_add_id(hipStream_t s, const tdesc & a, const tdesc & b, const tdesc & ids, const tdesc & dst);
 
 // ---- batched MUL_MAT over a 3-D quantised weight, one matrix per head: the absorbed MLA matrices of the deepseek2 graph (mmb.hip)
 struct mmb_args {
@@ -270,6 +274,8 @@ void launch_binary(hipStream_t s, int op, const tdesc & a, const tdesc & b, cons
 void launch_scale(hipStream_t s, const tdesc & src, const tdesc & dst, float scale, float bias);
 void launch_unary(hipStream_t s, int uop, const tdesc & src, const tdesc & dst);
 void launch_swiglu(hipStream_t s, const tdesc & a, const tdesc * b, const tdesc & dst, int swapped);
+// SWIGLU_OAI (gpt-oss): x = min(g, limit), y = clamp(u, -limit, limit), out = (x / (1 + expf(alpha * -x))) * (y + 1) with the C library's expf; operands as launch_swiglu's
+void launch_swiglu_oai(hipStream_t s, const tdesc & a, const tdesc * b, const tdesc & dst, int swapped, float alpha, float limit);
 // producers fused with the Q8_K activation quantisation (quantize.hip): the f32 intermediate is not written
 // the same with the row ASSEMBLED first from split-K partials (+ epilogue add) — and written out as f32, for its other readers
 struct splitk_src { const float * part; int ks; int64_t mn; const float * add; int64_t add_stride; float * out; int64_t out_stride; };

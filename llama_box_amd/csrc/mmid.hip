@@ -13,7 +13,14 @@
 // chunk) pairs in the same order, the same 6-step butterfly — so a (slot, token) result is bit-equal to the backend's own one-column
 // MUL_MAT over that expert's 2-D view.  An id outside [0, n_expert) reads nothing of `as` and writes zeros (ggml-cpu asserts there).
 // Larger batches are the same launch with more pairs: each pair streams its expert matrix again (out of L2 / MALL when experts repeat).
+//
+// ADD_ID (the per-expert bias gpt-oss puts behind each MUL_MAT_ID): dst(:, slot, token) = a(:, slot, token) + b(:, ids(slot, token)), ids read on the device as
+// above; an id outside [0, n_expert) adds nothing.  k_add_id is the node on its own; when it directly follows its MUL_MAT_ID (graph.cpp decides), the bias rides in
+// that launch's store instead (mmid_args::bias): acc + b[id][row] is the same single f32 addition, so both forms give the same bits, and an id outside the experts
+// stores the zeros the unfused pair would.
 #include <hip/hip_runtime.h>
+
+#include <algorithm>
 
 #include "mmvq_types.h"
 #include "kv_quant.h"
@@ -41,6 +48,7 @@ __global__ void __launch_bounds__(256) k_mmid(const mmid_args a) {
         return;
     }
     const uint8_t * W = a.W + (size_t) id * a.w_nb2;
+    const float * bias = a.bias ? (const float *) (a.bias + (size_t) id * a.bias_nb1) : nullptr;  // (ADD_ID in the store)
 
     // the first weight loads go out before the activations are touched (as k_mmvq)
     const uint8_t * rows[R];
@@ -85,7 +93,7 @@ __global__ void __launch_bounds__(256) k_mmid(const mmid_args a) {
 #pragma unroll
     for (int r = 0; r < R; ++r) {
         const float v = wave_sum(acc[r]);
-        if (lane == 0 && row0 + r < a.N) dcol[row0 + r] = v;
+        if (lane == 0 && row0 + r < a.N) dcol[row0 + r] = bias ? v + bias[row0 + r] : v;
     }
 }
 
@@ -139,7 +147,24 @@ __global__ void __launch_bounds__(256) k_mmid_f(const mmid_args a, const int vec
         }
     }
     acc = wave_sum(acc);
-    if (lane == 0) *out = acc;
+    if (lane == 0) *out = a.bias ? acc + ((const float *) (a.bias + (size_t) id * a.bias_nb1))[row] : acc;
+}
+
+// ADD_ID on its own: one workgroup per (slot, token) row of a; every thread reads its own elements before it writes them (dst may be a's block)
+__global__ void __launch_bounds__(256) k_add_id(const tdesc a, const tdesc b, const tdesc ids, const tdesc d) {
+    const int64_t pair = blockIdx.x, tok = pair / a.ne[1], slot = pair - tok * a.ne[1];
+    const float * x = (const float *) (a.data + slot * a.nb[1] + tok * a.nb[2]);
+    float * y = (float *) (d.data + slot * d.nb[1] + tok * d.nb[2]);
+    const int id = *(const int32_t *) (ids.data + tok * ids.nb[1] + slot * 4);
+    const bool in = (unsigned) id < (unsigned) b.ne[1];
+    const float * br = (const float *) (b.data + (in ? (int64_t) id : 0) * b.nb[1]);
+    for (int64_t i = (int64_t) blockIdx.y * 256 + threadIdx.x; i < a.ne[0]; i += (int64_t) gridDim.y * 256) y[i] = in ? x[i] + br[i] : x[i];
+}
+void launch_add_id(hipStream_t s, const tdesc & a, const tdesc & b, const tdesc & ids, const tdesc & d) {
+    const int64_t pairs = a.ne[1] * a.ne[2];
+    if (pairs < 1 || a.ne[0] < 1) return;
+    const unsigned chunks = (unsigned) std::min<int64_t>(64, (a.ne[0] + 1023) / 1024);
+    hipLaunchKernelGGL(k_add_id, dim3((unsigned) pairs, chunks), dim3(256), 0, s, a, b, ids, d);
 }
 
 template <typename T> static void launch_mmid_t(hipStream_t s, const mmid_args & a) {
@@ -177,6 +202,7 @@ void launch_mmid(hipStream_t s, const mmid_args & a) {
         case GGML_TYPE_Q5_1: launch_mmid_t<T_Q51>(s, a); break;
         case GGML_TYPE_IQ4_NL: launch_mmid_t<T_IQ4NL>(s, a); break;
         case GGML_TYPE_IQ4_XS: launch_mmid_t<T_IQ4XS>(s, a); break;
+        case GGML_TYPE_MXFP4: launch_mmid_t<T_MXFP4>(s, a); break;
         case GGML_TYPE_F16: case GGML_TYPE_BF16: case GGML_TYPE_F32: {
             const bool w16 = a.type == GGML_TYPE_F16;
             const bool vec_ok = (a.K % 8) == 0 && ((((uintptr_t) a.W) | ((uintptr_t) a.x) | (uintptr_t) a.w_nb1 | (uintptr_t) a.w_nb2 | (uintptr_t) a.x_nb1 | (uintptr_t) a.x_nb2) & 15) == 0;

@@ -517,7 +517,7 @@ template <typename T> static void launch_type(hipStream_t s, const mmvq_args & a
             return;
         }
     }
-    if constexpr (mmvq_is_l32_t<T>::value) {  // Q4_0 .. IQ4_NL: no prologue forms (their activations arrive quantised: graph.cpp never asks)
+    if constexpr (mmvq_no_prologue_t<T>::value) {  // Q4_0 .. IQ4_NL, MXFP4: no prologue forms (their activations arrive quantised: graph.cpp never asks)
         if (a0.x != nullptr || a0.fa_part != nullptr) { MI_ERR("launch_mmvq: weight type %d has no activation prologue", a0.type); abort(); }
     } else if (a0.x != nullptr || a0.fa_part != nullptr) {
         if ((a0.K % 256) != 0) {
@@ -617,6 +617,7 @@ void launch_mmvq(hipStream_t s, const mmvq_args & a, int rows_per_wave) {
         case GGML_TYPE_Q5_1: launch_type<T_Q51>(s, a, rows_per_wave); break;
         case GGML_TYPE_IQ4_NL: launch_type<T_IQ4NL>(s, a, rows_per_wave); break;
         case GGML_TYPE_IQ4_XS: launch_type<T_IQ4XS>(s, a, rows_per_wave); break;
+        case GGML_TYPE_MXFP4: launch_type<T_MXFP4>(s, a, rows_per_wave); break;
         default: MI_ERR("launch_mmvq: unsupported weight type %d", a.type); abort();
     }
 }

@@ -484,6 +484,57 @@ typedef T_L32<GGML_TYPE_IQ4_NL> T_IQ4NL;
 template <typename T> struct mmvq_is_l32_t : std::false_type {};
 template <int TYPE> struct mmvq_is_l32_t<T_L32<TYPE>> : std::true_type {};
 
+// ------------------------------------------------------------------------------------------------ MXFP4
+// ggml's block_mxfp4 (gpt-oss expert matrices): {u8 e, u8 qs[16]} = 17 bytes per 32 values, the nibble order of Q4_0 / IQ4_NL (value j < 16 the LOW nibble of qs[j],
+// value j + 16 its HIGH nibble), a nibble an index into {0, 1, 2, 3, 4, 6, 8, 12 | 0, -1, -2, -3, -4, -6, -8, -12} (E2M1 doubled), the block scale half of 2^(e - 127).
+// One lane owns ONE block, as T_L32 does.  A 17-byte block starts at ANY byte address (a row of K = 2880 is 1530 bytes; a K = 32 matrix has rows at 0, 17, 34 ...),
+// so the 16 code bytes are one load typed with 1-byte alignment — hipcc emits ONE global_load_dwordx4 for it on gfx950 (unaligned access mode; read in the
+// disassembly of this file's kernels) — and the scale byte a second load; a wave's 64 blocks are 1088 consecutive bytes.
+// Bit 3 of a nibble is the sign half of the table: two byte permutes a dword, as for IQ4_NL; then T_L32's dot4 chain and one f32 term per block in the reference's
+// expression (dy * scale) * sumi — the scale is a power of two, so the term is exact however it is associated (inside the f32 range).
+// No activation prologue (the activations arrive as Q8_0 blocks), no decode copy, no matrix-core form: 9 columns and more are passes of the mat-vec kernel.
+typedef mi_u32x4 mi_u32x4_a1 __attribute__((aligned(1)));
+struct __attribute__((packed, aligned(1))) u128_a1 { uint32_t x, y, z, w; };
+__device__ __forceinline__ u128_a1 ld_stream(const u128_a1 * p) { return ld_stream_as<u128_a1, mi_u32x4_a1>(p); }
+struct T_MXFP4 {
+    typedef q80_dev act;
+    static constexpr int BLK = 32, BYTES = 17, PPB = 1;
+    struct raw { u128_a1 q; uint32_t e; };
+    static constexpr int DW = 5;
+    static __device__ __forceinline__ raw load(const uint8_t * __restrict__ row, int p, int = 0) {
+        const uint8_t * blk = row + (size_t) p * BYTES;
+        raw r;
+        r.e = blk[0];
+        r.q = ld_stream((const u128_a1 *) (blk + 1));
+        return r;
+    }
+    template <int NC> static __device__ __forceinline__ void dot(const raw & r, int p, const act * __restrict__ y, int nblk, float * acc) {
+        const float d = __uint_as_float(mxfp4_scale_bits(r.e));
+        const uint32_t q[4] = {r.q.x, r.q.y, r.q.z, r.q.w};
+        uint32_t lo[4], hi[4];  // table bytes of values 4k .. 4k + 3 and 16 + 4k .. 16 + 4k + 3
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            lo[k] = mxfp4_bytes(q[k] & 0x0F0F0F0Fu);
+            hi[k] = mxfp4_bytes((q[k] >> 4) & 0x0F0F0F0Fu);
+        }
+#pragma unroll
+        for (int col = 0; col < NC; ++col) {
+            const act * yb = y + (size_t) col * nblk + p;
+            const int * yq = (const int *) yb->qs;
+            int s = 0;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                s = dot4((int) lo[k], yq[k], s);
+                s = dot4((int) hi[k], yq[4 + k], s);
+            }
+            acc[col] += (yb->d * d) * (float) s;
+        }
+    }
+};
+// the formats without an activation prologue in the mat-vec kernels (launch_type refuses the request)
+template <typename T> struct mmvq_no_prologue_t : mmvq_is_l32_t<T> {};
+template <> struct mmvq_no_prologue_t<T_MXFP4> : std::true_type {};
+
 // ------------------------------------------------------------------------------------------------ the plane layouts of the decode copy (see the top of this file)
 // (a row whose super-block count is not a multiple of 8 — Qwen2-7B: 14 and 74 — ends in a SHORT group of nb = nblk % 8 super-blocks with the same plane order,
 // 4 nb lanes wide; only its lines are shared between planes)

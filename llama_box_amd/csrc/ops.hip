@@ -293,6 +293,39 @@ void launch_swiglu(hipStream_t s, const tdesc & a, const tdesc * b, const tdesc 
     else hipLaunchKernelGGL(k_swiglu<false>, grid, dim3(256), 0, s, pa, pb, d.data, nc, a.nb[1], nbb1, d.nb[1]);
 }
 
+// SWIGLU_OAI (ggml_compute_forward_swiglu_oai_f32's scalar loop): every operation rounded on its own (this file is built without contraction), expf the C
+// library's — the result is the CPU's bit for bit, NaN where it gives NaN: min and clamp are std::min / std::clamp there, comparisons that hand a NaN operand
+// through (fminf / fmaxf would drop it), and are written out as those comparisons here.  One thread an element; rows at any byte stride, so every form (split 2-D / dense 3-D, one tensor,
+// swapped) is this kernel.
+__global__ void __launch_bounds__(256) k_swiglu_oai(const char * __restrict__ pg, const char * __restrict__ pu, char * __restrict__ pd, const int64_t nc,
+                                                    const int64_t nbg1, const int64_t nbu1, const int64_t nbd1, const float alpha, const float limit) {
+    const int64_t row = blockIdx.x;
+    const float * g = (const float *) (pg + row * nbg1);
+    const float * u = (const float *) (pu + row * nbu1);
+    float * y = (float *) (pd + row * nbd1);
+    for (int64_t i = (int64_t) blockIdx.y * 256 + threadIdx.x; i < nc; i += (int64_t) gridDim.y * 256) {
+        const float gv = g[i], uv = u[i];
+        const float x = limit < gv ? limit : gv;                              // std::min(g, limit)
+        const float yv = uv < -limit ? -limit : (limit < uv ? limit : uv);   // std::clamp(u, -limit, limit)
+        const float e = expf_libm(alpha * (-x));
+        const float out_glu = x / (1.0f + e);
+        y[i] = out_glu * (yv + 1.0f);
+    }
+}
+void launch_swiglu_oai(hipStream_t s, const tdesc & a, const tdesc * b, const tdesc & d, int swapped, float alpha, float limit) {
+    const int64_t rows = a.ne[1] * a.ne[2] * a.ne[3];
+    const int64_t nc = d.ne[0];
+    if (rows < 1 || nc < 1) return;
+    const char * pg = a.data;
+    const char * pu = b ? b->data : a.data;
+    if (!b) {
+        pg += swapped ? nc * 4 : 0;
+        pu += swapped ? 0 : nc * 4;
+    }
+    const dim3 grid((unsigned) rows, (unsigned) std::min<int64_t>(64, (nc + 1023) / 1024));
+    hipLaunchKernelGGL(k_swiglu_oai, grid, dim3(256), 0, s, pg, pu, d.data, nc, a.nb[1], b ? b->nb[1] : a.nb[1], d.nb[1], alpha, limit);
+}
+
 // ------------------------------------------------------------------------------------------------ CPY / DUP / CONT
 // ggml_compute_forward_dup: same logical element order on both sides, f32/f16 conversion (RNE)
 template <typename TS, typename TDST> __device__ __forceinline__ TDST conv(TS v);
@@ -400,6 +433,12 @@ __device__ __forceinline__ float dequant_elem(const int type, const uint8_t * __
             const int c = b[8 + 16 * ib + (j & 15)];
             const float dl = h2f(ld16(b)) * (float) (ls - 32);
             return dl * (float) k_iq4nl_values[j < 16 ? (c & 0xF) : (c >> 4)];
+        }
+        case GGML_TYPE_MXFP4: {
+            // {e, qs[16]}: value j is the low (j < 16) or high nibble of qs[j & 15] through the doubled E2M1 table, times half of 2^(e - 127): one exact product
+            const uint8_t * b = row + (i >> 5) * 17;
+            const int j = (int) (i & 31), c = b[1 + (j & 15)];
+            return mxfp4_value((uint32_t) (j < 16 ? (c & 0xF) : (c >> 4))) * __uint_as_float(mxfp4_scale_bits(b[0]));
         }
         case GGML_TYPE_Q4_0: case GGML_TYPE_Q4_1: case GGML_TYPE_Q5_0: case GGML_TYPE_Q5_1: case GGML_TYPE_IQ4_NL: {
             // dequantize_row_* through the octet helpers the KV cache in these formats is read with (kv_dequant.h): level * d (+ m), one rounding an operation

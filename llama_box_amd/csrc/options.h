@@ -62,6 +62,8 @@ namespace mi355x {
 // One per-backend switch is kept beside the table: ssm_fuse (backend_ctx::ssm_fuse, default on, GGML_MI355X_SSM_FUSE, set_option("ssm_fuse", 0 / 1)): SSM_CONV ->
 // ADD(bias) -> SILU as one launch.  tests/test_options_host.py holds the table's rows as a written-down contract that is extended on purpose, in a change of its own;
 // until then the switch is no row: backend.cpp reads the variable and stores the value next to the keys that are no field of c->opt.
+// mmid_bias (backend_ctx::mmid_bias, default on, GGML_MI355X_MMID_BIAS, set_option("mmid_bias", 0 / 1)) is kept the same way: MUL_MAT_ID -> ADD_ID as one launch, the bias
+// added in the store (graph.cpp, mmid.hip).
 
 struct options {
 #define MI_X(type, name, def, flag, env) type name = def;

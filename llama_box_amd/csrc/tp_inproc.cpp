@@ -555,6 +555,7 @@ static bool analyse_node(analysis & A, const ggml_tensor * t) {
     switch (t->op) {
         case GGML_OP_MUL_MAT: {
             if (mm_batched_q_ok(t)) return A.fail("a mat-mul over one quantised matrix per head, which the engine has no rule for", t);  // (as it has none for the SSM ops)
+            if (s0->type == GGML_TYPE_MXFP4) return A.fail("a mat-mul over an MXFP4 matrix, which the engine has no rule for", t);  // (gpt-oss expert blocks: MUL_MAT_ID / ADD_ID are declined below as unknown ops)
             if (!get_desc(A, s0, a) || !get_desc(A, s1, b)) return false;
             if (buffer_is_split(s0->buffer)) {
                 const split_tensor_info * info = split_info(s0);

@@ -419,6 +419,13 @@ static ggml_tensor * glu_impl(ggml_context * ctx, ggml_tensor * a, ggml_tensor *
 }
 struct ggml_tensor * ggml_swiglu(struct ggml_context * ctx, struct ggml_tensor * a) { return glu_impl(ctx, a, nullptr, GGML_GLU_OP_SWIGLU, false); }
 struct ggml_tensor * ggml_swiglu_split(struct ggml_context * ctx, struct ggml_tensor * a, struct ggml_tensor * b) { return glu_impl(ctx, a, b, GGML_GLU_OP_SWIGLU, false); }
+// gpt-oss's gated unit (ggml_swiglu_oai): the split form, alpha and limit as f32 in op_params[2..3]
+struct ggml_tensor * ggml_swiglu_oai(struct ggml_context * ctx, struct ggml_tensor * a, struct ggml_tensor * b, float alpha, float limit) {
+    ggml_tensor * r = glu_impl(ctx, a, b, GGML_GLU_OP_SWIGLU_OAI, false);
+    set_f32(r, 2, alpha);
+    set_f32(r, 3, limit);
+    return r;
+}
 // the other gated units: one tensor (halves of a row; _swapped: the gate comes first) or two (_split)
 #define LITE_GLU(name, OP) \
     struct ggml_tensor * ggml_##name(struct ggml_context * ctx, struct ggml_tensor * a) { return glu_impl(ctx, a, nullptr, OP, false); } \
@@ -591,6 +598,19 @@ struct ggml_tensor * ggml_mul_mat_id(struct ggml_context * ctx, struct ggml_tens
     return r;
 }
 
+// the per-expert bias behind a MUL_MAT_ID (ggml_add_id): dst(:, s, t) = a(:, s, t) + b(:, ids(s, t))
+struct ggml_tensor * ggml_add_id(struct ggml_context * ctx, struct ggml_tensor * a, struct ggml_tensor * b, struct ggml_tensor * ids) {
+    LITE_ASSERT(a->ne[0] == b->ne[0]);
+    LITE_ASSERT(a->ne[1] == ids->ne[0]);
+    LITE_ASSERT(a->ne[2] == ids->ne[1]);
+    LITE_ASSERT(ids->type == GGML_TYPE_I32);
+    ggml_tensor * r = ggml_new_tensor(ctx, a->type, 4, a->ne);
+    r->op = GGML_OP_ADD_ID;
+    r->src[0] = a;
+    r->src[1] = b;
+    r->src[2] = ids;
+    return r;
+}
 // state-space layers (llama.cpp build_mamba_layer / build_mamba2_layer)
 struct ggml_tensor * ggml_concat(struct ggml_context * ctx, struct ggml_tensor * a, struct ggml_tensor * b, int dim) {
     LITE_ASSERT(dim >= 0 && dim < GGML_MAX_DIMS);

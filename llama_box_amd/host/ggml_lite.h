@@ -87,6 +87,7 @@ struct ggml_tensor * ggml_silu(struct ggml_context * ctx, struct ggml_tensor * a
 struct ggml_tensor * ggml_unary(struct ggml_context * ctx, struct ggml_tensor * a, enum ggml_unary_op op);
 struct ggml_tensor * ggml_swiglu(struct ggml_context * ctx, struct ggml_tensor * a);
 struct ggml_tensor * ggml_swiglu_split(struct ggml_context * ctx, struct ggml_tensor * a, struct ggml_tensor * b);
+struct ggml_tensor * ggml_swiglu_oai(struct ggml_context * ctx, struct ggml_tensor * a, struct ggml_tensor * b, float alpha, float limit);
 struct ggml_tensor * ggml_gelu(struct ggml_context * ctx, struct ggml_tensor * a);
 struct ggml_tensor * ggml_gelu_quick(struct ggml_context * ctx, struct ggml_tensor * a);
 struct ggml_tensor * ggml_gelu_erf(struct ggml_context * ctx, struct ggml_tensor * a);
@@ -127,6 +128,7 @@ struct ggml_tensor * ggml_sum_rows(struct ggml_context * ctx, struct ggml_tensor
 struct ggml_tensor * ggml_clamp(struct ggml_context * ctx, struct ggml_tensor * a, float min, float max);  /* in place: a view of a */
 /* as [K, N, n_expert], b [K, n_used | 1, n_tokens] f32, ids [n_used, n_tokens] i32 -> [N, n_used, n_tokens] */
 struct ggml_tensor * ggml_mul_mat_id(struct ggml_context * ctx, struct ggml_tensor * as, struct ggml_tensor * b, struct ggml_tensor * ids);
+struct ggml_tensor * ggml_add_id(struct ggml_context * ctx, struct ggml_tensor * a, struct ggml_tensor * b, struct ggml_tensor * ids);
 /* state-space layers (llama.cpp build_mamba_layer / build_mamba2_layer; DESIGN.md §4i states the three contracts) */
 struct ggml_tensor * ggml_concat(struct ggml_context * ctx, struct ggml_tensor * a, struct ggml_tensor * b, int dim);
 /* sx [d_conv - 1 + n_t, d_inner, n_s], c [d_conv, d_inner] -> [d_inner, n_t, n_s] */
