@@ -25,7 +25,7 @@
 
 namespace mi355x {
 
-template <int W> __device__ __forceinline__ float group_sum(float v) {
+template <int W> __device__ __forceinline__ float mmb_group_sum(float v) {
     if constexpr (W == 16) return row16_sum(v);
     if constexpr (W == 8) v += __shfl_xor(v, 4, 64);
     v += dpp_f32<MI_DPP_QUAD_XOR2>(v);
@@ -88,7 +88,7 @@ __global__ void __launch_bounds__(256) k_mmb(const mmb_args a) {
     for (int c = 0; c < NC; ++c) {
         float v;
         if constexpr (W == 64) v = wave_sum(acc[c]);
-        else v = group_sum<W>(acc[c]);
+        else v = mmb_group_sum<W>(acc[c]);
         if (sub == 0 && row < a.N && c < live) out[(size_t) c * a.N] = v;
     }
 }

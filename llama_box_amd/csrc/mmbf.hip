@@ -8,126 +8,16 @@
 // Forms (launch_mul_mat_bf16 / mul_mat_bf16_form decide in one place):
 //   k_mmv_bf16<NC, R, NT>   1 .. 8 columns: the weight stream.  The columns are staged ONCE per workgroup into LDS as bf16, a wave owns R rows
 //                           and keeps 8 16-byte loads (8 KiB) in flight ahead of the FMAs.
-//   k_mul_mat_bf16_mma16    few columns / few tiles over long rows: 16 x 16 tiles on v_mfma_f32_16x16x32_bf16 (twin of k_mul_mat_f16_mma16)
-//   k_mul_mat_bf16_mma      batches: 32 x 32 tiles on v_mfma_f32_32x32x16_bf16 (twin of k_mul_mat_f16_mma)
-//   k_mul_mat_bf16          the dot kernel (twin of k_mul_mat_f): unaligned operands, K % 8 != 0, broadcast batches
-// The A / B lane maps (k = 8 (lane >> 5) + j, resp. 8 (lane >> 4) + j) and the C / D maps of the bf16 instructions are those of the f16 ones,
-// so the addressing and the epilogues are mmf.hip's; the operand conversion and the instruction differ.
-#include <algorithm>
+//   k_mul_mat_mma16         few columns / few tiles over long rows: 16 x 16 tiles on v_mfma_f32_16x16x32_bf16
+//   k_mul_mat_mma           batches: 32 x 32 tiles on v_mfma_f32_32x32x16_bf16, src1 rounded in the loop or once ahead of it (k_round_bf16)
+//   k_mul_mat_dot           the dot kernel: unaligned operands, K % 8 != 0, broadcast batches
+// The last three are mm_dense.h's templates — the kernels mmf.hip runs over f16 operands — instantiated for elem_bf16; the streaming kernel, the rounding
+// launch, the form decision, the timing classes and the launchers are this file's own.
 #include <cstdlib>
 
-#include "dev_util.h"
-#include "kernels.h"
-#include "kv_quant.h"
+#include "mm_dense.h"
 
 namespace mi355x {
-
-__device__ __forceinline__ float bf2f(const uint32_t h) { return __uint_as_float(h << 16); }
-__device__ __forceinline__ uint32_t bf_pack2(const float lo, const float hi) { return (uint32_t) f2bf(lo) | ((uint32_t) f2bf(hi) << 16); }
-// 8 bf16 in a uint4 -> f32: the low half of a dword shifted up, the high half masked in place
-__device__ __forceinline__ void bf_unpack8(const uint4 t, float (&w)[8]) {
-    const uint32_t u[4] = {t.x, t.y, t.z, t.w};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        w[2 * i] = __uint_as_float(u[i] << 16);
-        w[2 * i + 1] = __uint_as_float(u[i] & 0xFFFF0000u);
-    }
-}
-__device__ __forceinline__ uint4 bf_round8(const uint4 p0, const uint4 p1) {  // 8 f32 (as bits) -> 8 bf16
-    uint4 o;
-    o.x = bf_pack2(__uint_as_float(p0.x), __uint_as_float(p0.y));
-    o.y = bf_pack2(__uint_as_float(p0.z), __uint_as_float(p0.w));
-    o.z = bf_pack2(__uint_as_float(p1.x), __uint_as_float(p1.y));
-    o.w = bf_pack2(__uint_as_float(p1.z), __uint_as_float(p1.w));
-    return o;
-}
-
-// ---- the dot kernel: k_mul_mat_f's layout (LPR lanes own a row, 64 / LPR rows per wave, 4 waves), bf16 arithmetic
-__global__ void __launch_bounds__(256) k_mul_mat_bf16(const tdesc a, const tdesc b, const tdesc d, const int lpr, const int vec_ok) {
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int rpw = 64 / lpr;  // rows per wave
-    const int sub = lane / lpr, sl = lane % lpr;
-    const int64_t i01 = ((int64_t) blockIdx.x * 4 + wave) * rpw + sub;
-    const int64_t i11 = blockIdx.y;
-    const int64_t i12 = blockIdx.z % b.ne[2], i13 = blockIdx.z / b.ne[2];
-    const int64_t i02 = i12 / (b.ne[2] / a.ne[2]), i03 = i13 / (b.ne[3] / a.ne[3]);
-    const int64_t K = a.ne[0];
-    const bool live = i01 < a.ne[1];
-    const int64_t r = live ? i01 : a.ne[1] - 1;
-    const char * wrow = a.data + r * a.nb[1] + i02 * a.nb[2] + i03 * a.nb[3];
-    const char * xcol = b.data + i11 * b.nb[1] + i12 * b.nb[2] + i13 * b.nb[3];
-    float acc = 0.0f;
-    if (vec_ok) {
-        for (int64_t k = (int64_t) sl * 8; k < K; k += (int64_t) lpr * 8) {
-            float w[8], x[8];
-            bf_unpack8(*(const uint4 *) (wrow + k * 2), w);
-            bf_unpack8(bf_round8(*(const uint4 *) (xcol + k * 4), *(const uint4 *) (xcol + k * 4 + 16)), x);
-#pragma unroll
-            for (int i = 0; i < 8; ++i) acc = fmaf(w[i], x[i], acc);
-        }
-    } else {
-        for (int64_t k = sl; k < K; k += lpr) {
-            const float wv = bf2f(*(const uint16_t *) (wrow + k * a.nb[0]));
-            const float xv = bf2f(f2bf(*(const float *) (xcol + k * b.nb[0])));
-            acc = fmaf(wv, xv, acc);
-        }
-    }
-    for (int o = lpr >> 1; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
-    if (live && sl == 0) *(float *) (d.data + i01 * d.nb[0] + i11 * d.nb[1] + i12 * d.nb[2] + i13 * d.nb[3]) = acc;
-}
-
-// ---- batches: k_mul_mat_f16_mma's 32 x 32 tiles (A: src1 column m = lane & 31, B: src0 row n = lane & 31, k-group lane >> 5)
-typedef __bf16 mmbf_bf8 __attribute__((ext_vector_type(8)));
-typedef float mmbf_float16 __attribute__((ext_vector_type(16)));
-typedef float mmbf_float4 __attribute__((ext_vector_type(4)));
-// XBF: src1 was rounded to bf16 once by k_round_bf16 ([M][K] bf16 in scratch, described by `b`): one 16-byte load a step and no conversion in the loop
-template <bool XBF>
-__global__ void __launch_bounds__(256) k_mul_mat_bf16_mma(const tdesc a, const tdesc b, const tdesc d) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int r32 = lane & 31, g = lane >> 5;
-    const int64_t row0 = ((int64_t) blockIdx.x * 2 + (wave & 1)) * 32, col0 = ((int64_t) blockIdx.y * 2 + (wave >> 1)) * 32;
-    if (row0 >= a.ne[1] || col0 >= b.ne[1]) return;
-    const int64_t i12 = blockIdx.z % b.ne[2], i13 = blockIdx.z / b.ne[2];
-    const int64_t i02 = i12 / (b.ne[2] / a.ne[2]), i03 = i13 / (b.ne[3] / a.ne[3]);
-    const int64_t K = a.ne[0];
-    const char * wrow = a.data + std::min<int64_t>(row0 + r32, a.ne[1] - 1) * a.nb[1] + i02 * a.nb[2] + i03 * a.nb[3] + g * 16;  // this lane's src0 row, its k-group
-    const char * xcol = b.data + std::min<int64_t>(col0 + r32, b.ne[1] - 1) * b.nb[1] + i12 * b.nb[2] + i13 * b.nb[3] + g * (XBF ? 16 : 32);  // this lane's src1 column
-    mmbf_float16 acc = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    for (int64_t k = 0; k < K; k += 64) {  // 4 steps of 16 per trip, their loads in flight together
-        // k-group g of a step past the end (the last step of a K that is 8 mod 16 has no second group): the row's first group is fetched instead and masked to zeros
-        uint4 w[4], x0[4], x1[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int64_t kk = k + 16 * u;
-            const bool in = kk + 8 * g < K;
-            const int64_t kc = in ? kk : -8 * g;
-            const uint32_t keep = in ? 0xFFFFFFFFu : 0u;
-            w[u] = *(const uint4 *) (wrow + kc * 2);
-            w[u].x &= keep; w[u].y &= keep; w[u].z &= keep; w[u].w &= keep;
-            if constexpr (XBF) {
-                x0[u] = *(const uint4 *) (xcol + kc * 2);
-                x1[u] = x0[u];
-            } else {
-                x0[u] = *(const uint4 *) (xcol + kc * 4);
-                x1[u] = *(const uint4 *) (xcol + kc * 4 + 16);
-                x1[u].x &= keep; x1[u].y &= keep; x1[u].z &= keep; x1[u].w &= keep;
-            }
-            x0[u].x &= keep; x0[u].y &= keep; x0[u].z &= keep; x0[u].w &= keep;
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u)
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(mmbf_bf8, XBF ? x0[u] : bf_round8(x0[u], x1[u])), __builtin_bit_cast(mmbf_bf8, w[u]), acc, 0, 0, 0);
-    }
-    // lane: src0 row row0 + r32; register i: src1 column col0 + (i & 3) + 8 (i >> 2) + 4 g
-    const int64_t row = row0 + r32;
-    if (row >= a.ne[1]) return;
-    char * out = d.data + row * d.nb[0] + i12 * d.nb[2] + i13 * d.nb[3];
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-        const int64_t col = col0 + (i & 3) + 8 * (i >> 2) + 4 * g;
-        if (col < b.ne[1]) *(float *) (out + col * d.nb[1]) = acc[i];
-    }
-}
 
 // src1 [K, M] f32 (rows 16-byte aligned, K % 8 == 0) -> [M][K] bf16: one thread per 8 values
 __global__ void __launch_bounds__(256) k_round_bf16(const char * __restrict__ X, const int64_t x_nb1, uint4 * __restrict__ out, const int ng, const int64_t total) {
@@ -135,60 +25,11 @@ __global__ void __launch_bounds__(256) k_round_bf16(const char * __restrict__ X,
     if (i >= total) return;
     const int64_t c = i / ng, g = i - c * ng;
     const char * xp = X + c * x_nb1 + g * 32;
-    out[i] = bf_round8(*(const uint4 *) xp, *(const uint4 *) (xp + 16));
-}
-
-// ---- few output tiles over long rows, or 2 .. 15 columns: k_mul_mat_f16_mma16's 16 x 16 tiles, the NWK waves of a workgroup take the K steps of ONE tile in
-// turn and add up through LDS in wave order
-template <int NWK>
-__global__ void __launch_bounds__(64 * NWK) k_mul_mat_bf16_mma16(const tdesc a, const tdesc b, const tdesc d) {
-    __shared__ mmbf_float4 red[NWK][64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int r16 = lane & 15, kg = lane >> 4;
-    const int64_t row0 = (int64_t) blockIdx.x * 16, col0 = (int64_t) blockIdx.y * 16;
-    const int64_t i12 = blockIdx.z % b.ne[2], i13 = blockIdx.z / b.ne[2];
-    const int64_t i02 = i12 / (b.ne[2] / a.ne[2]), i03 = i13 / (b.ne[3] / a.ne[3]);
-    const int64_t K = a.ne[0];
-    const char * wrow = a.data + std::min<int64_t>(row0 + r16, a.ne[1] - 1) * a.nb[1] + i02 * a.nb[2] + i03 * a.nb[3] + kg * 16;
-    const char * xcol = b.data + std::min<int64_t>(col0 + r16, b.ne[1] - 1) * b.nb[1] + i12 * b.nb[2] + i13 * b.nb[3] + kg * 32;
-    mmbf_float4 acc = {0, 0, 0, 0};
-    for (int64_t k = (int64_t) wave * 32; k < K; k += 32 * NWK * 4) {  // 4 steps' loads in flight
-        uint4 w[4], x0[4], x1[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int64_t kk = k + (int64_t) u * 32 * NWK;
-            const bool in = kk + 8 * kg < K;  // past the end: fetch the row's first group instead (no branch between the loads) and mask it to zeros
-            const int64_t kc = in ? kk : -8 * kg;
-            const uint32_t keep = in ? 0xFFFFFFFFu : 0u;
-            w[u] = *(const uint4 *) (wrow + kc * 2);
-            x0[u] = *(const uint4 *) (xcol + kc * 4);
-            x1[u] = *(const uint4 *) (xcol + kc * 4 + 16);
-            w[u].x &= keep; w[u].y &= keep; w[u].z &= keep; w[u].w &= keep;
-            x0[u].x &= keep; x0[u].y &= keep; x0[u].z &= keep; x0[u].w &= keep;
-            x1[u].x &= keep; x1[u].y &= keep; x1[u].z &= keep; x1[u].w &= keep;
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u)
-            acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(mmbf_bf8, bf_round8(x0[u], x1[u])), __builtin_bit_cast(mmbf_bf8, w[u]), acc, 0, 0, 0);
-    }
-    red[wave][lane] = acc;
-    __syncthreads();
-    if (wave != 0) return;
-#pragma unroll
-    for (int w = 1; w < NWK; ++w) acc += red[w][lane];
-    // lane: src0 row row0 + r16; register i: src1 column col0 + 4 kg + i
-    const int64_t row = row0 + r16;
-    if (row >= a.ne[1]) return;
-    char * out = d.data + row * d.nb[0] + i12 * d.nb[2] + i13 * d.nb[3];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int64_t col = col0 + 4 * kg + i;
-        if (col < b.ne[1]) *(float *) (out + col * d.nb[1]) = acc[i];
-    }
+    out[i] = elem_bf16::round8(*(const uint4 *) xp, *(const uint4 *) (xp + 16));
 }
 
 // ---- 1 .. 8 columns: the weight stream.  A decode step of a bf16 model reads every weight once (16 GB a token at 8 B parameters) and does two flops a byte: the
-// kernel is its loads.  The dot kernel above gives a wave one or two dependent 1-KiB loads at a time; here
+// kernel is its loads.  The dot kernel gives a wave one or two dependent 1-KiB loads at a time; here
 //   * the grid is a fixed number of workgroups (two a CU, fewer when the rows do not fill them) that stay for the whole matrix: a workgroup (4 waves) rounds the
 //     M <= NC activation columns to bf16 ONCE into LDS ([NC][K] bf16 — no quantise launch, no prologue: the rounding IS the staging) and its waves then walk
 //     groups of R consecutive rows, wave w of W taking groups w, w + W, ... (neighbouring waves read neighbouring rows at any one time),
@@ -229,7 +70,7 @@ __global__ void __launch_bounds__(256) k_mmv_bf16(const char * __restrict__ W, c
         uint4 o = make_uint4(0, 0, 0, 0);
         if (c < M) {
             const char * xp = X + (size_t) c * x_nb1 + (size_t) g * 32;
-            o = bf_round8(*(const uint4 *) xp, *(const uint4 *) (xp + 16));
+            o = elem_bf16::round8(*(const uint4 *) xp, *(const uint4 *) (xp + 16));
         }
         *(uint4 *) (smem + (size_t) i * 16) = o;
     }
@@ -261,12 +102,12 @@ __global__ void __launch_bounds__(256) k_mmv_bf16(const char * __restrict__ W, c
             for (int r = 0; r < R; ++r) {
                 uint4 q = w[t][r];
                 q.x &= keep; q.y &= keep; q.z &= keep; q.w &= keep;
-                bf_unpack8(q, wf[r]);
+                elem_bf16::unpack8(q, wf[r]);
             }
 #pragma unroll
             for (int c = 0; c < NC; ++c) {
                 float xf[8];
-                bf_unpack8(*(const uint4 *) (smem + ((size_t) c * ng + gc) * 16), xf);
+                elem_bf16::unpack8(*(const uint4 *) (smem + ((size_t) c * ng + gc) * 16), xf);
 #pragma unroll
                 for (int r = 0; r < R; ++r)
 #pragma unroll
@@ -299,17 +140,17 @@ __global__ void __launch_bounds__(256) k_mmv_bf16(const char * __restrict__ W, c
 // ------------------------------------------------------------------------------------------------ routing
 #define MMV_LDS_MAX (64 * 1024)
 
-static bool mmbf_vec_ok(const tdesc & a, const tdesc & b) {
-    const int64_t K = a.ne[0];
-    bool ok = a.nb[0] == 2 && b.nb[0] == 4 && (K % 8) == 0 && (((uintptr_t) a.data) & 15) == 0 && (((uintptr_t) b.data) & 15) == 0;
-    for (int i = 1; i < 4; ++i) ok = ok && (a.nb[i] % 16) == 0 && (b.nb[i] % 16) == 0;
-    return ok;
+// widest column chunk of the streaming kernel whose staged columns ([cap][K] bf16) fit one launch's LDS
+static int mmv_col_cap(const int64_t K) {
+    int cap = 8;
+    while (cap > 1 && (int64_t) cap * K * 2 > MMV_LDS_MAX) cap >>= 1;
+    return cap;
 }
 // force: MI_BF16_* to measure or test a form where it can serve the operands (else the form decided here), -1 = decide; max_cols: the widest batch the streaming
 // kernel takes (0 .. 8, the hand-over to the 16 x 16 tiles; 0: never — the dot kernel serves one column)
 int mul_mat_bf16_form(const tdesc & a, const tdesc & b, const tdesc & d, const int force, const int max_cols) {
     const int64_t K = a.ne[0], N = a.ne[1], M = b.ne[1];
-    if (!mmbf_vec_ok(a, b) || force == MI_BF16_DOT) return MI_BF16_DOT;
+    if (!mm_vec_ok(a, b, 2) || force == MI_BF16_DOT) return MI_BF16_DOT;
     const bool flat = a.ne[2] == 1 && a.ne[3] == 1 && b.ne[2] == 1 && b.ne[3] == 1 && d.nb[0] == 4 && (d.nb[1] % 4) == 0;
     const bool mmv_ok = flat && K * 2 <= MMV_LDS_MAX && K <= INT32_MAX / 16 && N <= INT32_MAX / 8 && M <= 65535;
     if (force == MI_BF16_MMA16 || force == MI_BF16_MMA) return force;
@@ -364,9 +205,8 @@ template <int NC> static void launch_mmv_nc(hipStream_t s, const tdesc & a, cons
 }
 // columns in chunks of the widest NC whose staged columns fit LDS; the weights are streamed once a chunk
 static void launch_mmv(hipStream_t s, const tdesc & a, const tdesc & b, const tdesc & d, const bool nt) {
-    const int64_t K = a.ne[0], M = b.ne[1];
-    int cap = 8;
-    while (cap > 1 && (int64_t) cap * K * 2 > MMV_LDS_MAX) cap >>= 1;
+    const int64_t M = b.ne[1];
+    const int cap = mmv_col_cap(a.ne[0]);
     for (int64_t c0 = 0; c0 < M; c0 += cap) {
         const int m = (int) std::min<int64_t>(cap, M - c0);
         const char * x = b.data + c0 * b.nb[1];
@@ -380,14 +220,13 @@ static void launch_mmv(hipStream_t s, const tdesc & a, const tdesc & b, const td
 }
 int mul_mat_bf16_launches(const int form, const tdesc & a, const tdesc & b) {
     if (form != MI_BF16_MMV && form != MI_BF16_MMV_COLS) return 1;
-    int cap = 8;
-    while (cap > 1 && (int64_t) cap * a.ne[0] * 2 > MMV_LDS_MAX) cap >>= 1;
+    const int cap = mmv_col_cap(a.ne[0]);
     return (int) ((b.ne[1] + cap - 1) / cap);
 }
 
 // scratch of the 32 x 32 tile form with src1 rounded to bf16 once ahead of the launch (0: the operands do not take that form)
 size_t mul_mat_bf16_workspace_bytes(const tdesc & a, const tdesc & b) {
-    if (!mmbf_vec_ok(a, b) || a.ne[2] != 1 || a.ne[3] != 1 || b.ne[2] != 1 || b.ne[3] != 1 || b.ne[1] < 64) return 0;
+    if (!mm_vec_ok(a, b, 2) || a.ne[2] != 1 || a.ne[3] != 1 || b.ne[2] != 1 || b.ne[3] != 1 || b.ne[1] < 64) return 0;
     return (size_t) (b.ne[1] * a.ne[0] * 2);
 }
 // form: what mul_mat_bf16_form answered for these operands (< 0: asked here, with the defaults); nt: the weight loads of the streaming kernel carry the
@@ -399,12 +238,9 @@ void launch_mul_mat_bf16(hipStream_t s, const tdesc & a, const tdesc & b, const 
         case MI_BF16_MMV: case MI_BF16_MMV_COLS:
             launch_mmv(s, a, b, d, nt);
             return;
-        case MI_BF16_MMA16: {
-            dim3 grid((unsigned) ((a.ne[1] + 15) / 16), (unsigned) ((b.ne[1] + 15) / 16), (unsigned) (b.ne[2] * b.ne[3]));
-            if (K >= 4096) hipLaunchKernelGGL(k_mul_mat_bf16_mma16<16>, grid, dim3(1024), 0, s, a, b, d);
-            else hipLaunchKernelGGL(k_mul_mat_bf16_mma16<8>, grid, dim3(512), 0, s, a, b, d);
+        case MI_BF16_MMA16:
+            launch_mul_mat_mma16<elem_bf16>(s, a, b, d);
             return;
-        }
         case MI_BF16_MMA: {
             dim3 grid((unsigned) ((a.ne[1] + 63) / 64), (unsigned) ((b.ne[1] + 63) / 64), (unsigned) (b.ne[2] * b.ne[3]));
             const size_t need = ws ? mul_mat_bf16_workspace_bytes(a, b) : 0;
@@ -418,24 +254,15 @@ void launch_mul_mat_bf16(hipStream_t s, const tdesc & a, const tdesc & b, const 
                 xb.nb[1] = (size_t) K * 2;
                 xb.nb[2] = xb.nb[1] * (size_t) b.ne[1];
                 xb.nb[3] = xb.nb[2];
-                hipLaunchKernelGGL(k_mul_mat_bf16_mma<true>, grid, dim3(256), 0, s, a, xb, d);
+                hipLaunchKernelGGL((k_mul_mat_mma<elem_bf16, true>), grid, dim3(256), 0, s, a, xb, d);
                 return;
             }
-            hipLaunchKernelGGL(k_mul_mat_bf16_mma<false>, grid, dim3(256), 0, s, a, b, d);
+            hipLaunchKernelGGL((k_mul_mat_mma<elem_bf16, false>), grid, dim3(256), 0, s, a, b, d);
             return;
         }
         default: break;
     }
-    const bool vec_ok = mmbf_vec_ok(a, b);
-    int lpr = 64;
-    if (vec_ok) {
-        while (lpr > 8 && (int64_t) (lpr / 2) * 8 >= K) lpr >>= 1;
-    } else {
-        while (lpr > 8 && (int64_t) (lpr / 2) >= K) lpr >>= 1;
-    }
-    const int rows_per_block = 4 * (64 / lpr);
-    dim3 grid((unsigned) ((a.ne[1] + rows_per_block - 1) / rows_per_block), (unsigned) b.ne[1], (unsigned) (b.ne[2] * b.ne[3]));
-    hipLaunchKernelGGL(k_mul_mat_bf16, grid, dim3(256), 0, s, a, b, d, lpr, vec_ok ? 1 : 0);
+    launch_mul_mat_dot<elem_bf16>(s, a, b, d, mm_vec_ok(a, b, 2));
 }
 
 MI_TU_TOUCH(mmbf)

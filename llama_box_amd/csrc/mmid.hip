@@ -21,9 +21,10 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <type_traits>
 
+#include "mm_dense.h"
 #include "mmvq_types.h"
-#include "kv_quant.h"
 
 namespace mi355x {
 
@@ -97,12 +98,11 @@ __global__ void __launch_bounds__(256) k_mmid(const mmid_args a) {
     }
 }
 
-// f16 / bf16 / f32 experts: k_mul_mat_f's product (f32 activations rounded to the weights' 16-bit format first — f16, or bf16 through f2bf as ggml-cpu's
-// from_float does —, f32 fmaf accumulation), one wave per row.  WT: 0 f32, 1 f16, 2 bf16
-__device__ __forceinline__ float mmid_bf2f(const uint16_t h) { return __uint_as_float((uint32_t) h << 16); }
+// f16 / bf16 / f32 experts: the dot kernel's product (mm_dense.h: f32 activations rounded to the weights' 16-bit format first — f16, or bf16 through f2bf as
+// ggml-cpu's from_float does —, f32 fmaf accumulation), one wave per row.  WT: 0 f32, 1 f16, 2 bf16
 template <int WT>
 __global__ void __launch_bounds__(256) k_mmid_f(const mmid_args a, const int vec_ok) {
-    constexpr bool W16 = WT == 1, WBF = WT == 2;
+    typedef std::conditional_t<WT == 1, elem_f16, std::conditional_t<WT == 2, elem_bf16, elem_f32>> E;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int row = blockIdx.x * 4 + wave;
     const int pair = blockIdx.y, tok = pair / a.n_used, slot = pair - tok * a.n_used;
@@ -119,30 +119,24 @@ __global__ void __launch_bounds__(256) k_mmid_f(const mmid_args a, const int vec
     float acc = 0.0f;
     if (vec_ok) {
         for (int k = lane * 8; k < K; k += 64 * 8) {
-            float w[8];
-            if (W16 || WBF) {
+            float w[8], x[8];
+            if constexpr (E::SIZE == 2) {  // (E::load8, written out: filled through a reference, the bf16 instantiation's FMAs are scheduled differently)
                 const uint4 t = *(const uint4 *) (wrow + (size_t) k * 2);
                 const uint32_t u[4] = {t.x, t.y, t.z, t.w};
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
-                    w[2 * i] = WBF ? mmid_bf2f((uint16_t) (u[i] & 0xFFFF)) : h2f((uint16_t) (u[i] & 0xFFFF));
-                    w[2 * i + 1] = WBF ? mmid_bf2f((uint16_t) (u[i] >> 16)) : h2f((uint16_t) (u[i] >> 16));
+                    w[2 * i] = E::cvt1((uint16_t) (u[i] & 0xFFFF));
+                    w[2 * i + 1] = E::cvt1((uint16_t) (u[i] >> 16));
                 }
-            } else {
-                const float4 t0 = *(const float4 *) (wrow + (size_t) k * 4), t1 = *(const float4 *) (wrow + (size_t) k * 4 + 16);
-                w[0] = t0.x; w[1] = t0.y; w[2] = t0.z; w[3] = t0.w; w[4] = t1.x; w[5] = t1.y; w[6] = t1.z; w[7] = t1.w;
-            }
-            const float4 x0 = *(const float4 *) (xcol + (size_t) k * 4), x1 = *(const float4 *) (xcol + (size_t) k * 4 + 16);
-            const float x[8] = {x0.x, x0.y, x0.z, x0.w, x1.x, x1.y, x1.z, x1.w};
+            } else E::load8(wrow + (size_t) k * E::SIZE, w);
+            elem_f32::load8(xcol + (size_t) k * 4, x);
 #pragma unroll
-            for (int i = 0; i < 8; ++i) acc = fmaf(w[i], WBF ? mmid_bf2f(f2bf(x[i])) : (W16 ? h2f(f2h(x[i])) : x[i]), acc);
+            for (int i = 0; i < 8; ++i) acc = fmaf(w[i], E::round1(x[i]), acc);
         }
     } else {
         for (int k = lane; k < K; k += 64) {
-            const float wv = WBF ? mmid_bf2f(*(const uint16_t *) (wrow + (size_t) k * 2)) : (W16 ? h2f(*(const uint16_t *) (wrow + (size_t) k * 2)) : *(const float *) (wrow + (size_t) k * 4));
-            float xv = *(const float *) (xcol + (size_t) k * 4);
-            if (W16) xv = h2f(f2h(xv));
-            if (WBF) xv = mmid_bf2f(f2bf(xv));
+            const float wv = E::load1(wrow + (size_t) k * E::SIZE);
+            const float xv = E::round1(*(const float *) (xcol + (size_t) k * 4));
             acc = fmaf(wv, xv, acc);
         }
     }

@@ -25,6 +25,7 @@ void launch_splitk_reduce(hipStream_t s, const float * part, int ks, int M, int 
     const int64_t mn = (int64_t) M * N;
     hipLaunchKernelGGL(p_reduce, dim3((unsigned) ((mn / 4 + 255) / 256)), dim3(256), 0, s, part, ks, mn, dst);
 }
+void launch_mul_mat_bf16(hipStream_t, const tdesc &, const tdesc &, const tdesc &, int, bool, void *, size_t) {}  // (mmbf.hip is not part of the probe: no bf16 operand here)
 }
 using namespace mi355x;
 
@@ -39,7 +40,7 @@ template <int VAR> __global__ void __launch_bounds__(256) p_short(const tdesc a,
     float x[G][8];
 #pragma unroll
     for (int g = 0; g < G; ++g) {
-        if (kin && VAR != 1) mmf_x8(b.data + (i02 * G + g) * b.nb[2] + (int64_t) sl * 32, x[g]);
+        if (kin && VAR != 1) elem_f16::x8(b.data + (i02 * G + g) * b.nb[2] + (int64_t) sl * 32, x[g]);
         else
 #pragma unroll
             for (int i = 0; i < 8; ++i) x[g][i] = 1.0f + lane;
@@ -48,7 +49,7 @@ template <int VAR> __global__ void __launch_bounds__(256) p_short(const tdesc a,
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
         const int64_t row = std::min<int64_t>(base + 4 * rpw * r, a.ne[1] - 1);
-        if (kin && VAR != 2) mmf_w8(a.data + row * a.nb[1] + i02 * a.nb[2] + (int64_t) sl * 16, w[r]);
+        if (kin && VAR != 2) elem_f16::load8(a.data + row * a.nb[1] + i02 * a.nb[2] + (int64_t) sl * 16, w[r]);
         else
 #pragma unroll
             for (int i = 0; i < 8; ++i) w[r][i] = 0.5f * lane;
@@ -61,7 +62,7 @@ template <int VAR> __global__ void __launch_bounds__(256) p_short(const tdesc a,
             float acc = 0.0f;
 #pragma unroll
             for (int i = 0; i < 8; ++i) acc = fmaf(w[r][i], x[g][i], acc);
-            if (VAR == 5) acc = group_sum<16>(acc);
+            if (VAR == 5) acc = mmf_group_sum<16>(acc);
             else if (VAR != 4) for (int o = lpr >> 1; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
             if (VAR == 3) { if (acc == 12345.678f) *(float *) d.data = acc; }
             else if (sl == 0 && row < a.ne[1]) *(float *) (d.data + row * d.nb[0] + (i02 * G + g) * d.nb[2]) = acc;
@@ -195,7 +196,7 @@ int main() {
         const tdesc tm2 = mk(mask, GGML_TYPE_F16, n_kv, 64, 1, 2, n_kv * 2, n_kv * 2 * 64);
         (void) tm2;
         timeit("batch 32 x 7296: K.Q (launch_mul_mat_f)", [&] { launch_mul_mat_f(0, k2, tq2, tkq2); });
-        timeit("batch 32 x 7296: K.Q tile kernel (no resident columns)", [&] { dim3 grid((ncell + 63) / 64, 1, NH); hipLaunchKernelGGL(k_mul_mat_f16_mma, grid, dim3(256), 0, 0, k2, tq2, tkq2); });
+        timeit("batch 32 x 7296: K.Q tile kernel (no resident columns)", [&] { dim3 grid((ncell + 63) / 64, 1, NH); hipLaunchKernelGGL((k_mul_mat_mma<elem_f16, false>), grid, dim3(256), 0, 0, k2, tq2, tkq2); });
         timeit("batch 32 x 7296: soft_max (no mask)", [&] { launch_soft_max(0, tkq2, nullptr, nullptr, tp2, 0.088f, 0.0f); });
         timeit("batch 32 x 7296: V^T.p with scratch (K cut over workgroups + reduce)", [&] { launch_mul_mat_f(0, v2, tp2, to2, (float *) ws2, 64u << 20); });
         timeit("batch 32 x 7296: V^T.p without scratch (16 x 16 tiles, K over waves)", [&] { launch_mul_mat_f(0, v2, tp2, to2); });

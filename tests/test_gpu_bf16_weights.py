@@ -1,5 +1,5 @@
 """GPU tests for weight matrices kept in bf16: acceptance and what stays refused, MUL_MAT on every kernel form of csrc/mmbf.hip (the streaming
-mat-vec, its multi-column form, 16 x 16 and 32 x 32 matrix-core tiles, the dot kernel's vector and scalar paths), exact integer products, a read-back of the
+mat-vec, its multi-column form, 16 x 16 and 32 x 32 matrix-core tiles, the dot kernel's vector and scalar paths), bit-equal sums of one matrix stored as f16 and as bf16 on the kernels the two formats share, exact integer products, a read-back of the
 activation rounding, weight value edges, GET_ROWS, MUL_MAT_ID, a norm output shared with quantised matrices, and the bf16 test models.
 
 The reference is the CPU oracle (vec_dot_type(BF16) = BF16: activations rounded by fp32_to_bf16, products summed in double).  Gates are the project's own: NMSE <= 1e-11
@@ -247,8 +247,43 @@ def test_tiles_over_prerounded_columns(backend, plog, shape):
     assert np.array_equal(got.view(np.uint32), plain.view(np.uint32))
 
 
+# ---------------------------------------------------------------------------------------------- the f16 and bf16 forms are one kernel
+def _both_formats_exact(shape, rng):
+    """float32 values exact in f16 AND bf16: at most 8 significant bits (bf16's width), exponents 2^-6 .. 2^4 (well inside f16's range), random signs"""
+    return (rng.integers(128, 256, shape) * np.exp2(rng.integers(-13, -2, shape)) * rng.choice([-1.0, 1.0], shape)).astype(np.float32)
+
+
+# (K, N, M), the bf16 form to force (-1: routed).  K = 136 ends in the 8-mod-16 tail, N = 65 leaves a one-row edge tile; the f16 side routes itself: (136, 40, 1)
+# falls through to the dot kernel (fewer than 64 rows), K = 7 fails the vector conditions, 4 columns take the 16 x 16 tiles and 33 the 32 x 32 ones
+TWINS = [("dot_vector", (136, 40, 1), DOT), ("dot_scalar", (7, 65, 3), -1), ("mma16", (136, 65, 4), MMA16), ("mma", (136, 65, 33), -1)]
+
+
+@pytest.mark.parametrize("pair,shape,form", TWINS, ids=[t[0] for t in TWINS])
+def test_f16_and_bf16_forms_sum_in_the_same_order(backend, plog, pair, shape, form):
+    """One matrix stored as F16 and as BF16, its values and the activations exact in both formats (so both roundings are the identity): the twin kernels share
+    their addressing, loop and reduction, hence the f32 summation order — the two products are equal bit for bit.  The exponent spread makes the f32 sums inexact,
+    so a different order WOULD show: at least one output differs from the double-precision sum rounded to f32."""
+    K, N, M = shape
+    rng = np.random.default_rng(4000 + K + 7 * N + 31 * M)
+    Wf, X = _both_formats_exact((N, K), rng), _both_formats_exact((M, K), rng)
+    W16, Wbf = Wf.astype(np.float16), B.to_bf16(Wf)
+    for v in (Wf, X):  # both conversions round-trip the inputs
+        assert np.array_equal(v.astype(np.float16).astype(np.float32), v) and np.array_equal(B.from_bf16(B.to_bf16(v)), v)
+    H = L.host()
+    (g16,), c16 = _run_timed(backend, lambda g: H.ggml_mul_mat(g.ctx, g.new(L.F16, [K, N], W16, name="w"), g.new(L.F32, [K, M], X, name="x")))
+    (gbf,), cbf = _run_timed(backend, lambda g: B.g_mul_mat(g, Wbf, X, K, N, M), form)
+    exact = (X.astype(np.float64) @ Wf.astype(np.float64).T).astype(np.float32)
+    g16, gbf = g16.reshape(M, N), gbf.reshape(M, N)
+    n_inexact = int(np.count_nonzero(g16 != exact))
+    n_diff = int(np.count_nonzero(g16.view(np.uint32) != gbf.view(np.uint32)))
+    plog(f"f16 / bf16 twins {pair} K={K} N={N} M={M}: {c16} / {cbf}; {n_diff} of {g16.size} outputs differ between the formats, {n_inexact} differ from the exact sum rounded")
+    assert c16 == ["mul_mat_f"] and cbf == [{"dot_vector": "mul_mat_bf16_dot", "dot_scalar": "mul_mat_bf16_dot", "mma16": "mul_mat_bf16_mma16", "mma": "mul_mat_bf16_mma"}[pair]], (c16, cbf)
+    assert n_inexact > 0
+    assert n_diff == 0, np.argwhere(g16.view(np.uint32) != gbf.view(np.uint32))[:4]
+
+
 # ---------------------------------------------------------------------------------------------- exact on small integers
-EXACT = [(1, -1), (2, -1), (3, -1), (8, -1), (8, MMV_COLS), (12, -1), (40, -1), (40, MMA), (12, MMA16), (3, DOT), (3, MMA16), (1, DOT)]
+EXACT =[(1, -1), (2, -1), (3, -1), (8, -1), (8, MMV_COLS), (12, -1), (40, -1), (40, MMA), (12, MMA16), (3, DOT), (3, MMA16), (1, DOT)]
 
 
 @pytest.mark.parametrize("M,form", EXACT, ids=lambda v: str(v))
