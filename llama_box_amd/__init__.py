@@ -37,6 +37,8 @@ ROPE_NEOX = 2
 SORT_ORDER_ASC, SORT_ORDER_DESC = 0, 1  # ggml_argsort
 ROPE_MROPE = 8    # ggml_rope_multi: four position streams over sections of the rotation pairs (Qwen2-VL)
 ROPE_VISION = 24  # mrope with independent sections, pairs (i, i + n_dims) over the whole row (vision towers)
+POOL_MAX, POOL_AVG = 0, 1  # ggml_pool_1d / ggml_pool_2d
+SCALE_NEAREST, SCALE_BILINEAR, SCALE_BICUBIC, SCALE_ALIGN_CORNERS = 0, 1, 2, 1 << 8  # ggml_upscale / ggml_interpolate: the mode, and the flag or-ed into it
 
 
 def build(verbose=False):
@@ -138,6 +140,9 @@ _SIGS = {
     "ggml_sqr": (TP, [_P, TP]), "ggml_repeat": (TP, [_P, TP, TP]), "ggml_l2_norm": (TP, [_P, TP, _F]),
     "ggml_rwkv_wkv6": (TP, [_P, TP, TP, TP, TP, TP, TP]), "ggml_rwkv_wkv7": (TP, [_P, TP, TP, TP, TP, TP, TP, TP]),
     "ggml_gated_linear_attn": (TP, [_P, TP, TP, TP, TP, TP, _F]),
+    "ggml_im2col": (TP, [_P, TP, TP, _I, _I, _I, _I, _I, _I, _B, _I]), "ggml_conv_1d": (TP, [_P, TP, TP, _I, _I, _I]), "ggml_conv_2d": (TP, [_P, TP, TP, _I, _I, _I, _I, _I, _I]),
+    "ggml_pool_1d": (TP, [_P, TP, _I, _I, _I, _I]), "ggml_pool_2d": (TP, [_P, TP, _I, _I, _I, _I, _I, _F, _F]), "ggml_pad": (TP, [_P, TP, _I, _I, _I, _I]),
+    "ggml_upscale": (TP, [_P, TP, _I, _I]), "ggml_interpolate": (TP, [_P, TP, _I64, _I64, _I64, _I64, C.c_uint32]),
     "ggml_new_graph": (C.POINTER(CGraph), [_P]), "ggml_new_graph_custom": (C.POINTER(CGraph), [_P, _SZ, _B]),
     "ggml_build_forward_expand": (None, [C.POINTER(CGraph), TP]), "ggml_graph_n_nodes": (_I, [C.POINTER(CGraph)]),
     "ggml_graph_node": (TP, [C.POINTER(CGraph), _I]), "ggml_graph_view": (CGraph, [C.POINTER(CGraph), _I, _I]),

@@ -386,6 +386,84 @@ static bool repeat_ok(const ggml_tensor * op) {
     return true;
 }
 
+// The ops of a vision / audio tower's front end and projector tail (conv.hip; DESIGN.md §4m restates their contracts).  Shapes, types and strides only; whatever is
+// outside the stated contract is refused.
+static const int64_t CONV_MAX_ELEMS = (int64_t) 1 << 38;  // (one thread per element or vector, 256 a workgroup: the grid's x extent)
+// (a + 2 p - d (k - 1) - 1) / s + 1, or -1 where the window does not fit once
+static int64_t conv_out_extent(int64_t in, int64_t k, int s, int p, int d) {
+    const int64_t num = in + 2 * (int64_t) p - (int64_t) d * (k - 1) - 1;
+    return num < 0 ? -1 : num / s + 1;
+}
+// IM2COL: src = {kernel (extents only), data}; op_params {s0, s1, p0, p1, d0, d1, is_2D}.  2-D: kernel [KW, KH, IC, OC], data f32 [IW, IH, IC, N] with dense image
+// rows -> [IC * KH * KW, OW, OH, N]; 1-D: kernel [KW, IC, OC], data f32 [IW, IC, N] -> [IC * KW, OW, N, 1].  Channel and batch strides any multiple of 4; f16 / f32 result
+static bool im2col_ok(const ggml_tensor * op) {
+    const ggml_tensor * k = op->src[0], * x = op->src[1];
+    if (!k || !x || x->type != GGML_TYPE_F32 || (op->type != GGML_TYPE_F16 && op->type != GGML_TYPE_F32) || !ggml_abi_is_contiguous(op)) return false;
+    const int32_t * q = op->op_params;
+    const bool is_2d = q[6] != 0;
+    if (q[0] <= 0 || q[2] < 0 || q[4] <= 0 || x->nb[0] != 4 || (x->nb[1] % 4) || (x->nb[2] % 4) || (x->nb[3] % 4)) return false;
+    for (int d = 0; d < 4; ++d) if (k->ne[d] < 1 || x->ne[d] < 1) return false;
+    if (ggml_abi_nelements(op) > CONV_MAX_ELEMS) return false;
+    const int64_t OW = conv_out_extent(x->ne[0], k->ne[0], q[0], q[2], q[4]);
+    if (is_2d) {
+        if (q[1] <= 0 || q[3] < 0 || q[5] <= 0 || x->nb[1] != (size_t) x->ne[0] * 4 || k->ne[2] != x->ne[2]) return false;
+        const int64_t OH = conv_out_extent(x->ne[1], k->ne[1], q[1], q[3], q[5]);
+        return OW >= 1 && OH >= 1 && op->ne[0] == k->ne[2] * k->ne[1] * k->ne[0] && op->ne[1] == OW && op->ne[2] == OH && op->ne[3] == x->ne[3];
+    }
+    if (k->ne[3] != 1 || x->ne[3] != 1 || k->ne[1] != x->ne[1]) return false;
+    return OW >= 1 && op->ne[0] == k->ne[1] * k->ne[0] && op->ne[1] == OW && op->ne[2] == x->ne[2] && op->ne[3] == 1;
+}
+// MUL_MAT with an f16 src1 (the convolution kernel behind an IM2COL): src0 f16 too, both with contiguous elements and every other stride a multiple of 2, the usual
+// dim-2 / 3 broadcast, an f32 contiguous result.  Any other src0 type with an f16 src1 stays refused, and so does every other src1 type that is not f32
+static bool mm_f16x_ok(const ggml_tensor * op) {
+    const ggml_tensor * a = op->src[0], * b = op->src[1];
+    if (!a || !b || a->type != GGML_TYPE_F16 || b->type != GGML_TYPE_F16 || op->type != GGML_TYPE_F32 || !ggml_abi_is_contiguous(op)) return false;
+    if (buffer_is_split(a->buffer) || buffer_is_split(b->buffer) || a->nb[0] != 2 || b->nb[0] != 2) return false;
+    for (int d = 1; d < 4; ++d) if ((a->nb[d] % 2) || (b->nb[d] % 2)) return false;
+    for (int d = 0; d < 4; ++d) if (a->ne[d] < 1 || b->ne[d] < 1) return false;
+    if (a->ne[0] != b->ne[0] || b->ne[2] % a->ne[2] != 0 || b->ne[3] % a->ne[3] != 0) return false;
+    if (b->ne[1] > 65535 || b->ne[2] * b->ne[3] > 65535 || a->ne[1] > INT32_MAX / 2) return false;  // (the dot form's grid: y = columns, z = batches, x = row groups)
+    return op->ne[0] == a->ne[1] && op->ne[1] == b->ne[1] && op->ne[2] == b->ne[2] && op->ne[3] == b->ne[3];
+}
+// POOL_2D {op, k0, k1, s0, s1, p0, p1} -> [(W + 2 p0 - k0) / s0 + 1, (H + 2 p1 - k1) / s1 + 1, ne2, ne3]; POOL_1D {op, k0, s0, p0}, only k0 == s0 and p0 == 0 (all ggml-cpu
+// computes) -> [(W - k0) / s0 + 1, ne1, ne2, ne3].  op 0 MAX, 1 AVG; f32, source rows contiguous, the other strides any multiple of 4, the result contiguous
+static bool pool_ok(const ggml_tensor * op) {
+    const ggml_tensor * a = op->src[0];
+    if (!a || a->type != GGML_TYPE_F32 || !is_f32_contig(op) || a->nb[0] != 4 || (a->nb[1] % 4) || (a->nb[2] % 4) || (a->nb[3] % 4)) return false;
+    const int32_t * q = op->op_params;
+    if ((q[0] != 0 && q[0] != 1) || ggml_abi_nelements(op) > CONV_MAX_ELEMS) return false;
+    for (int d = 0; d < 4; ++d) if (a->ne[d] < 1) return false;
+    if (op->op == GGML_OP_POOL_1D) {
+        const int k0 = q[1], s0 = q[2], p0 = q[3];
+        if (k0 < 1 || s0 != k0 || p0 != 0 || a->ne[0] < k0) return false;
+        return op->ne[0] == (a->ne[0] - k0) / s0 + 1 && op->ne[1] == a->ne[1] && op->ne[2] == a->ne[2] && op->ne[3] == a->ne[3];
+    }
+    const int k0 = q[1], k1 = q[2], s0 = q[3], s1 = q[4], p0 = q[5], p1 = q[6];
+    if (k0 < 1 || k1 < 1 || s0 < 1 || s1 < 1 || p0 < 0 || p1 < 0 || (int64_t) k0 * k1 > (1 << 24)) return false;
+    if (a->ne[0] + 2 * (int64_t) p0 < k0 || a->ne[1] + 2 * (int64_t) p1 < k1) return false;
+    return op->ne[0] == (a->ne[0] + 2 * (int64_t) p0 - k0) / s0 + 1 && op->ne[1] == (a->ne[1] + 2 * (int64_t) p1 - k1) / s1 + 1 && op->ne[2] == a->ne[2] && op->ne[3] == a->ne[3];
+}
+// PAD: f32, the source with contiguous elements at any strides that are multiples of 4, the result contiguous with every extent >= the source's.  At this ABI snapshot the
+// node has no parameters; later ggml versions put left pads in op_params[0, 2, 4, 6] — a node where any of those is non-zero is refused
+static bool pad_ok(const ggml_tensor * op) {
+    const ggml_tensor * a = op->src[0];
+    if (!a || a->type != GGML_TYPE_F32 || !is_f32_contig(op) || a->nb[0] != 4 || ggml_abi_nelements(op) > CONV_MAX_ELEMS) return false;
+    for (int d = 0; d < 4; ++d)
+        if (a->ne[d] < 1 || op->ne[d] < a->ne[d] || (a->nb[d] % 4) || op->op_params[2 * d] != 0) return false;
+    return true;
+}
+// UPSCALE: f32, source rows contiguous, result contiguous; op_params[0]: mode in the low byte (0 nearest, 1 bilinear), bit 8 align-corners.  Nearest and bilinear
+// without align-corners are served; bicubic, align-corners and any other bit are refused.  Extents below 2^24: an index is exact as a float
+static bool upscale_ok(const ggml_tensor * op) {
+    const ggml_tensor * a = op->src[0];
+    if (!a || a->type != GGML_TYPE_F32 || !is_f32_contig(op) || a->nb[0] != 4 || ggml_abi_nelements(op) > CONV_MAX_ELEMS) return false;
+    const int32_t mode = op->op_params[0];
+    if (mode != 0 && mode != 1) return false;
+    for (int d = 0; d < 4; ++d)
+        if (a->ne[d] < 1 || op->ne[d] < 1 || a->ne[d] >= (1 << 24) || op->ne[d] >= (1 << 24) || (a->nb[d] % 4)) return false;
+    return true;
+}
+
 bool supports_op(const ggml_tensor * op) {
     const ggml_tensor * a = op->src[0];
     const ggml_tensor * b = op->src[1];
@@ -400,6 +478,7 @@ bool supports_op(const ggml_tensor * op) {
         case GGML_OP_NONE: case GGML_OP_VIEW: case GGML_OP_RESHAPE: case GGML_OP_PERMUTE: case GGML_OP_TRANSPOSE:
             return true;
         case GGML_OP_MUL_MAT: {
+            if (b && b->type == GGML_TYPE_F16) return mm_f16x_ok(op);  // (the convolution kernel behind an IM2COL: f16 x f16 only; every other src1 type but f32 is refused below)
             if (!a || !b || b->type != GGML_TYPE_F32 || op->type != GGML_TYPE_F32 || !ggml_abi_is_contiguous(op)) return false;
             if (buffer_is_split(a->buffer)) return split_mul_mat_supported(op);  // -sm row weights: every device computes its rows (split.cpp)
             if (mm_cache_image_ok(op)) return true;
@@ -493,6 +572,14 @@ bool supports_op(const ggml_tensor * op) {
             return is_f32_contig(a) && is_f32_contig(op);
         case GGML_OP_REPEAT:
             return repeat_ok(op);
+        case GGML_OP_IM2COL:
+            return im2col_ok(op);
+        case GGML_OP_POOL_1D: case GGML_OP_POOL_2D:
+            return pool_ok(op);
+        case GGML_OP_PAD:
+            return pad_ok(op);
+        case GGML_OP_UPSCALE:
+            return upscale_ok(op);
         default:
             return false;
     }
@@ -555,6 +642,8 @@ static ws_plan plan_ws(backend_ctx * c, const ggml_cgraph * g) {
         } else if (mm_image) {
             const tdesc a16 = kv_image_desc(TD(n->src[0]), nullptr);
             p.aux_bytes = std::max(p.aux_bytes, ((mul_mat_f_workspace_bytes(a16, TD(n->src[1])) + 255) & ~(size_t) 255) + kv_image_bytes(a16));
+        } else if (n->op == GGML_OP_MUL_MAT && n->src[1] && n->src[1]->type == GGML_TYPE_F16) {
+            // f16 x f16 (conv.hip): both forms add up in registers, no scratch
         } else if (n->op == GGML_OP_MUL_MAT && n->src[0]->type == GGML_TYPE_F16) {
             p.aux_bytes = std::max(p.aux_bytes, mul_mat_f_workspace_bytes(TD(n->src[0]), TD(n->src[1])));
             if (c->opt.attn_nf) p.aux_bytes = std::max(p.aux_bytes, attn_nf_list_scratch_bytes(TD(n->src[1]), TD(n->src[0]), nullptr));
@@ -2100,6 +2189,15 @@ static int run_node(exec_state & st, int i) {
         }
 
         case GGML_OP_MUL_MAT: {
+            if (b->type == GGML_TYPE_F16) {
+                // f16 x f16 (the product behind an IM2COL): its own launcher, asked first — no fusion scan, image or prologue below ever sees an f16 src1
+                if (!mm_f16x_ok(n)) { MI_ERR("graph_compute: node %d '%s': an f16 src1 outside the contract (DESIGN.md 4m; supports_op answers false for it)", i, n->name); return -1; }
+                const tdesc ta = TD(a), tb = TD(b);
+                timed_scope ts(c, mul_mat_f16x_runs_mma(ta, tb, c->conv_mma) ? "mul_mat_f16x_mma" : "mul_mat_f16x_dot", (double) ggml_abi_nbytes(a) + (double) ggml_abi_nbytes(b));
+                launch_mul_mat_f16x(s, ta, tb, TD(n), c->conv_mma);
+                c->st.kernel_launches++;
+                return 1;
+            }
             if (mm_runs_on_image(n)) {
                 // K.q over a cache kept in a block format / bf16 (-fa off): the view goes through its f16 image, the product through the f16 kernel
                 tdesc a16 = TD(a), none = TD(a);
@@ -2749,6 +2847,30 @@ static int run_node(exec_state & st, int i) {
             return 1;
         case GGML_OP_REPEAT:
             launch_repeat(s, TD(a), TD(n));
+            c->st.kernel_launches++;
+            return 1;
+        case GGML_OP_IM2COL: {
+            if (!im2col_ok(n)) { MI_ERR("graph_compute: node %d '%s' is outside IM2COL's contract (DESIGN.md 4m)", i, n->name); return -1; }
+            timed_scope ts(c, "im2col", (double) ggml_abi_nbytes(n) + (double) ggml_abi_nbytes(b));
+            if (!launch_im2col(s, TD(a), TD(b), TD(n), n->op_params)) return -1;
+            c->st.kernel_launches++;
+            return 1;
+        }
+        case GGML_OP_POOL_1D: case GGML_OP_POOL_2D: {
+            if (!pool_ok(n)) { MI_ERR("graph_compute: node %d '%s' is outside the pool ops' contract (DESIGN.md 4m)", i, n->name); return -1; }
+            timed_scope ts(c, n->op == GGML_OP_POOL_2D ? "pool_2d" : "pool_1d", (double) ggml_abi_nbytes(n) + (double) ggml_abi_nbytes(a));
+            if (!launch_pool(s, TD(a), TD(n), n->op_params, n->op == GGML_OP_POOL_2D)) return -1;
+            c->st.kernel_launches++;
+            return 1;
+        }
+        case GGML_OP_PAD:
+            if (!pad_ok(n)) { MI_ERR("graph_compute: node %d '%s' is outside PAD's contract (DESIGN.md 4m)", i, n->name); return -1; }
+            launch_pad(s, TD(a), TD(n));
+            c->st.kernel_launches++;
+            return 1;
+        case GGML_OP_UPSCALE:
+            if (!upscale_ok(n)) { MI_ERR("graph_compute: node %d '%s' is outside UPSCALE's contract (DESIGN.md 4m)", i, n->name); return -1; }
+            if (!launch_upscale(s, TD(a), TD(n), n->op_params[0])) return -1;
             c->st.kernel_launches++;
             return 1;
         default:

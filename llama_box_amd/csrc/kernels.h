@@ -445,6 +445,21 @@ void launch_l2_norm(hipStream_t s, const tdesc & src, const tdesc & dst, float e
 void launch_sqr(hipStream_t s, const tdesc & src, const tdesc & dst);
 void launch_repeat(hipStream_t s, const tdesc & src, const tdesc & dst);
 
+// ---- vision / audio towers (conv.hip; DESIGN.md 4m states the contracts, graph.cpp's im2col_ok / mm_f16x_ok / pool_ok / pad_ok / upscale_ok check them)
+// IM2COL: `kernel` is read for its extents only; src f32 with dense image rows; dst f16 / f32 contiguous; op_params {s0, s1, p0, p1, d0, d1, is_2D}
+bool launch_im2col(hipStream_t s, const tdesc & kernel, const tdesc & src, const tdesc & dst, const int32_t * op_params);
+// MUL_MAT with f16 src0 and f16 src1 (nothing rounded, f32 sums), dst f32 contiguous.  mma: the conv_mma switch (0 off, 1 routed, 2 forced); the matrix-core form
+// serves even K at rows aligned to 4 bytes or more — routed: from MI_CONV_MMA_MIN_TILES result tiles of 32 x 32 on —, the dot form (mm_dense.h's k_mul_mat_dot
+// reading 2-byte activations) everything else
+#define MI_CONV_MMA_MIN_TILES 32
+void launch_mul_mat_f16x(hipStream_t s, const tdesc & a, const tdesc & b, const tdesc & d, int mma);
+bool mul_mat_f16x_runs_mma(const tdesc & a, const tdesc & b, int mma);
+// POOL_2D (op_params {op, k0, k1, s0, s1, p0, p1}) / POOL_1D ({op, k0, s0, p0}); op 0 MAX, 1 AVG; f32, src rows contiguous, dst contiguous
+bool launch_pool(hipStream_t s, const tdesc & src, const tdesc & dst, const int32_t * op_params, bool is_2d);
+// PAD: src at the low indices of the contiguous dst, zero elsewhere; UPSCALE: mode 0 nearest, 1 bilinear without align-corners
+void launch_pad(hipStream_t s, const tdesc & src, const tdesc & dst);
+bool launch_upscale(hipStream_t s, const tdesc & src, const tdesc & dst, int mode);
+
 // ---- code-object preload (round 4).  The HIP runtime loads a translation unit's device code on the FIRST launch of one of its kernels
 // (0.3 - 2 ms each, measured as idle gaps in front of the first prompt's kernels: 5.5 ms of a 64 ms prefill).  Every kernel file ends with
 // MI_TU_TOUCH(name): an empty kernel + a launcher; init_backend launches them all once per device, so the cost moves to start-up.
@@ -472,6 +487,7 @@ void tu_touch_mmid(hipStream_t s);
 void tu_touch_mmb(hipStream_t s);
 void tu_touch_ssm(hipStream_t s);
 void tu_touch_rwkv(hipStream_t s);
+void tu_touch_conv(hipStream_t s);
 inline void preload_kernel_files(hipStream_t s) {
     tu_touch_kv_types(s);
     tu_touch_repack(s);
@@ -494,6 +510,7 @@ inline void preload_kernel_files(hipStream_t s) {
     tu_touch_tp_p2p(s);
     tu_touch_ssm(s);
     tu_touch_rwkv(s);
+    tu_touch_conv(s);
 }
 
 }  // namespace mi355x

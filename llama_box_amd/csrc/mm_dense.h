@@ -19,23 +19,24 @@ typedef float mm_float16 __attribute__((ext_vector_type(16)));
 typedef float mm_float4 __attribute__((ext_vector_type(4)));
 
 // ------------------------------------------------------------------------------------------------ element traits
-// SIZE: bytes of a stored element; cvt1 / load1 / unpack8 / load8: stored elements (bits, or at an address) -> f32; round1: the from_float round trip of one
+// SIZE: bytes of a stored element, XSIZE: of a src1 element; x1: one src1 element at an address -> f32 as the product takes it; cvt1 / load1 / unpack8 / load8: stored elements (bits, or at an address) -> f32; round1: the from_float round trip of one
 // activation, x8: of the eight at an address; vec8: the MFMA operand of eight, round8: eight f32 activations (as bits) -> the A operand; mfma32 / mfma16:
 // v_mfma_f32_32x32x16 / v_mfma_f32_16x16x32 (B = 16 bytes as loaded).  Each member is the conversion its kernels have always used, in the form they used it: the
 // kernels compile to the instruction streams they had before the formats shared a source (uint4 by reference for f16 and by value for bf16 is part of that).
 struct elem_f32 {  // (the dot kernels only: no rounding, no matrix-core form)
-    static constexpr int SIZE = 4;
+    static constexpr int SIZE = 4, XSIZE = 4;
     static __device__ __forceinline__ void load8(const char * p, float (&w)[8]) {
         const float4 t0 = *(const float4 *) p, t1 = *(const float4 *) (p + 16);
         w[0] = t0.x; w[1] = t0.y; w[2] = t0.z; w[3] = t0.w; w[4] = t1.x; w[5] = t1.y; w[6] = t1.z; w[7] = t1.w;
     }
     static __device__ __forceinline__ float load1(const char * p) { return *(const float *) p; }
     static __device__ __forceinline__ float round1(const float v) { return v; }
+    static __device__ __forceinline__ float x1(const char * p) { return *(const float *) p; }
     static __device__ __forceinline__ void x8(const char * p, float (&x)[8]) { load8(p, x); }
 };
 
 struct elem_f16 {
-    static constexpr int SIZE = 2;
+    static constexpr int SIZE = 2, XSIZE = 4;
     typedef _Float16 vec8 __attribute__((ext_vector_type(8)));
     static __device__ __forceinline__ float cvt1(const uint16_t h) { return h2f(h); }
     static __device__ __forceinline__ void unpack8(const uint4 & t, float (&w)[8]) {
@@ -49,6 +50,7 @@ struct elem_f16 {
     static __device__ __forceinline__ void load8(const char * p, float (&w)[8]) { unpack8(*(const uint4 *) p, w); }
     static __device__ __forceinline__ float load1(const char * p) { return cvt1(*(const uint16_t *) p); }
     static __device__ __forceinline__ float round1(const float v) { return h2f(f2h(v)); }
+    static __device__ __forceinline__ float x1(const char * p) { return round1(*(const float *) p); }
     static __device__ __forceinline__ void x8(const char * p, float (&x)[8]) {
         elem_f32::load8(p, x);
 #pragma unroll
@@ -70,7 +72,7 @@ struct elem_f16 {
 // (rounding: ggml_compute_fp32_to_bf16 — nearest even, subnormals kept, NaN kept quiet: f2bf of kv_quant.h, in integer arithmetic; a stored element is its 16
 // bits shifted up.  round8 hands the eight bf16 on as the uint4 they are packed into: the operand type appears at the instruction only)
 struct elem_bf16 {
-    static constexpr int SIZE = 2;
+    static constexpr int SIZE = 2, XSIZE = 4;
     typedef __bf16 vec8 __attribute__((ext_vector_type(8)));
     static __device__ __forceinline__ float cvt1(const uint16_t h) { return __uint_as_float((uint32_t) h << 16); }
     static __device__ __forceinline__ void unpack8(const uint4 t, float (&w)[8]) {  // the low half of a dword shifted up, the high half masked in place
@@ -84,6 +86,7 @@ struct elem_bf16 {
     static __device__ __forceinline__ void load8(const char * p, float (&w)[8]) { unpack8(*(const uint4 *) p, w); }
     static __device__ __forceinline__ float load1(const char * p) { return cvt1(*(const uint16_t *) p); }
     static __device__ __forceinline__ float round1(const float v) { return cvt1(f2bf(v)); }
+    static __device__ __forceinline__ float x1(const char * p) { return round1(*(const float *) p); }
     static __device__ __forceinline__ uint32_t pack2(const float lo, const float hi) { return (uint32_t) f2bf(lo) | ((uint32_t) f2bf(hi) << 16); }
     static __device__ __forceinline__ uint4 round8(const uint4 p0, const uint4 p1) {
         uint4 o;
@@ -100,6 +103,14 @@ struct elem_bf16 {
     static __device__ __forceinline__ mm_float4 mfma16(const uint4 & x, const uint4 & w, const mm_float4 acc) {
         return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(vec8, x), __builtin_bit_cast(vec8, w), acc, 0, 0, 0);
     }
+};
+
+// f16 src0 against an f16 src1 (the convolution kernel behind an IM2COL; conv.hip): ggml-cpu's vec_dot_type F16 when src1 already has that type — nothing is
+// rounded, an activation is read as the 2-byte element it is (the dot kernel only; the matrix-core form of this pair is conv.hip's own)
+struct elem_f16_x16 : elem_f16 {
+    static constexpr int XSIZE = 2;
+    static __device__ __forceinline__ float x1(const char * p) { return load1(p); }
+    static __device__ __forceinline__ void x8(const char * p, float (&x)[8]) { load8(p, x); }
 };
 
 // ------------------------------------------------------------------------------------------------ host helpers
@@ -139,14 +150,14 @@ __global__ void __launch_bounds__(256) k_mul_mat_dot(const tdesc a, const tdesc 
         for (int64_t k = (int64_t) sl * 8; k < K; k += (int64_t) lpr * 8) {
             float w[8], x[8];
             E::load8(wrow + k * E::SIZE, w);
-            E::x8(xcol + k * 4, x);
+            E::x8(xcol + k * E::XSIZE, x);
 #pragma unroll
             for (int i = 0; i < 8; ++i) acc = fmaf(w[i], x[i], acc);
         }
     } else {
         for (int64_t k = sl; k < K; k += lpr) {
             const float wv = E::load1(wrow + k * a.nb[0]);
-            const float xv = E::round1(*(const float *) (xcol + k * b.nb[0]));
+            const float xv = E::x1(xcol + k * b.nb[0]);
             acc = fmaf(wv, xv, acc);
         }
     }

@@ -64,6 +64,8 @@ namespace mi355x {
 // until then the switch is no row: backend.cpp reads the variable and stores the value next to the keys that are no field of c->opt.
 // mmid_bias (backend_ctx::mmid_bias, default on, GGML_MI355X_MMID_BIAS, set_option("mmid_bias", 0 / 1)) is kept the same way: MUL_MAT_ID -> ADD_ID as one launch, the bias
 // added in the store (graph.cpp, mmid.hip).
+// conv_mma (backend_ctx::conv_mma, default 1, GGML_MI355X_CONV_MMA, set_option("conv_mma", 0 / 1 / 2)) likewise: MUL_MAT f16 x f16, the product behind an IM2COL.
+// 1: on the matrix cores where the shape is routed there; 0: the dot form everywhere; 2: the matrix cores wherever the operands allow (A/B runs, tests; conv.hip).
 
 struct options {
 #define MI_X(type, name, def, flag, env) type name = def;

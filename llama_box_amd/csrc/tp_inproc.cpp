@@ -760,6 +760,8 @@ static bool analyse_node(analysis & A, const ggml_tensor * t) {
             return all_replicated();
         case GGML_OP_RWKV_WKV6: case GGML_OP_GATED_LINEAR_ATTN: case GGML_OP_RWKV_WKV7: case GGML_OP_L2_NORM: case GGML_OP_SQR: case GGML_OP_REPEAT:
             return A.fail("an op of a linear-attention recurrent layer, which the engine has no rule for", t);  // (as it has none for the SSM ops)
+        case GGML_OP_IM2COL: case GGML_OP_POOL_1D: case GGML_OP_POOL_2D: case GGML_OP_PAD: case GGML_OP_UPSCALE:
+            return A.fail("an op of a vision / audio tower, which the engine has no rule for", t);  // (a tower runs on the one device its projector lives on)
         default:
             return A.fail("an op the engine has no rule for", t);
     }

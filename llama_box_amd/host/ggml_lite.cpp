@@ -731,6 +731,78 @@ struct ggml_tensor * ggml_rwkv_wkv7(struct ggml_context * ctx, struct ggml_tenso
     return wkv_result(ctx, GGML_OP_RWKV_WKV7, src, 7);
 }
 
+// vision / audio towers (ggml.c: ggml_im2col, ggml_conv_1d, ggml_conv_2d, ggml_pool_1d, ggml_pool_2d, ggml_pad, ggml_interpolate_impl; DESIGN.md §4m states the contracts)
+static int64_t conv_output_size(int64_t ins, int64_t ks, int s, int p, int d) { return (ins + 2 * p - d * (ks - 1) - 1) / s + 1; }
+struct ggml_tensor * ggml_im2col(struct ggml_context * ctx, struct ggml_tensor * a, struct ggml_tensor * b, int s0, int s1, int p0, int p1, int d0, int d1, bool is_2D,
+                                 enum ggml_type dst_type) {
+    if (is_2D) LITE_ASSERT(a->ne[2] == b->ne[2]);
+    else LITE_ASSERT(a->ne[1] == b->ne[1] && b->ne[3] == 1);
+    const int64_t OH = is_2D ? conv_output_size(b->ne[1], a->ne[1], s1, p1, d1) : 0;
+    const int64_t OW = conv_output_size(b->ne[0], a->ne[0], s0, p0, d0);
+    LITE_ASSERT((!is_2D || OH > 0) && OW > 0);
+    const int64_t ne[4] = {is_2D ? a->ne[2] * a->ne[1] * a->ne[0] : a->ne[1] * a->ne[0], OW, is_2D ? OH : b->ne[2], is_2D ? b->ne[3] : 1};
+    ggml_tensor * r = ggml_new_tensor(ctx, dst_type, 4, ne);
+    const int32_t params[7] = {s0, s1, p0, p1, d0, d1, is_2D ? 1 : 0};
+    memcpy(r->op_params, params, sizeof(params));
+    r->op = GGML_OP_IM2COL;
+    r->src[0] = a;
+    r->src[1] = b;
+    return r;
+}
+struct ggml_tensor * ggml_conv_1d(struct ggml_context * ctx, struct ggml_tensor * a, struct ggml_tensor * b, int s0, int p0, int d0) {
+    ggml_tensor * im2col = ggml_im2col(ctx, a, b, s0, 0, p0, 0, d0, 0, false, a->type);  // [N, OL, IC * K]
+    ggml_tensor * r = ggml_mul_mat(ctx, ggml_reshape_2d(ctx, im2col, im2col->ne[0], im2col->ne[2] * im2col->ne[1]),  // [N * OL, IC * K]
+                                   ggml_reshape_2d(ctx, a, a->ne[0] * a->ne[1], a->ne[2]));                          // [OC, IC * K]
+    return ggml_reshape_3d(ctx, r, im2col->ne[1], a->ne[2], im2col->ne[2]);                                          // [N, OC, OL]
+}
+struct ggml_tensor * ggml_conv_2d(struct ggml_context * ctx, struct ggml_tensor * a, struct ggml_tensor * b, int s0, int s1, int p0, int p1, int d0, int d1) {
+    ggml_tensor * im2col = ggml_im2col(ctx, a, b, s0, s1, p0, p1, d0, d1, true, a->type);  // [N, OH, OW, IC * KH * KW]
+    ggml_tensor * r = ggml_mul_mat(ctx, ggml_reshape_2d(ctx, im2col, im2col->ne[0], im2col->ne[3] * im2col->ne[2] * im2col->ne[1]),  // [N * OH * OW, IC * KH * KW]
+                                   ggml_reshape_2d(ctx, a, a->ne[0] * a->ne[1] * a->ne[2], a->ne[3]));                               // [OC, IC * KH * KW]
+    r = ggml_reshape_4d(ctx, r, im2col->ne[1], im2col->ne[2], im2col->ne[3], a->ne[3]);  // [OC, N, OH, OW]
+    return ggml_cont(ctx, ggml_permute(ctx, r, 0, 1, 3, 2));                             // [N, OC, OH, OW]
+}
+static int64_t pool_output_size(int64_t ins, int ks, int s, float p) { return (int64_t) ((ins + 2 * p - ks) / s + 1); }
+struct ggml_tensor * ggml_pool_1d(struct ggml_context * ctx, struct ggml_tensor * a, enum ggml_op_pool op, int k0, int s0, int p0) {
+    const int64_t ne[4] = {pool_output_size(a->ne[0], k0, s0, (float) p0), a->ne[1], a->ne[2], a->ne[3]};
+    LITE_ASSERT(ne[0] > 0);
+    ggml_tensor * r = ggml_new_tensor(ctx, GGML_TYPE_F32, 4, ne);
+    const int32_t params[4] = {(int32_t) op, k0, s0, p0};
+    memcpy(r->op_params, params, sizeof(params));
+    r->op = GGML_OP_POOL_1D;
+    r->src[0] = a;
+    return r;
+}
+struct ggml_tensor * ggml_pool_2d(struct ggml_context * ctx, struct ggml_tensor * a, enum ggml_op_pool op, int k0, int k1, int s0, int s1, float p0, float p1) {
+    const int64_t ne[4] = {pool_output_size(a->ne[0], k0, s0, p0), pool_output_size(a->ne[1], k1, s1, p1), a->ne[2], a->ne[3]};
+    LITE_ASSERT(ne[0] > 0 && ne[1] > 0);
+    ggml_tensor * r = ggml_new_tensor(ctx, GGML_TYPE_F32, 4, ne);
+    const int32_t params[7] = {(int32_t) op, k0, k1, s0, s1, (int32_t) p0, (int32_t) p1};
+    memcpy(r->op_params, params, sizeof(params));
+    r->op = GGML_OP_POOL_2D;
+    r->src[0] = a;
+    return r;
+}
+struct ggml_tensor * ggml_pad(struct ggml_context * ctx, struct ggml_tensor * a, int p0, int p1, int p2, int p3) {
+    LITE_ASSERT(p0 >= 0 && p1 >= 0 && p2 >= 0 && p3 >= 0);
+    ggml_tensor * r = ggml_new_tensor_4d(ctx, a->type, a->ne[0] + p0, a->ne[1] + p1, a->ne[2] + p2, a->ne[3] + p3);
+    r->op = GGML_OP_PAD;
+    r->src[0] = a;
+    return r;
+}
+struct ggml_tensor * ggml_interpolate(struct ggml_context * ctx, struct ggml_tensor * a, int64_t ne0, int64_t ne1, int64_t ne2, int64_t ne3, uint32_t mode) {
+    LITE_ASSERT(ne0 > 0 && ne1 > 0 && ne2 > 0 && ne3 > 0);
+    ggml_tensor * r = ggml_new_tensor_4d(ctx, a->type, ne0, ne1, ne2, ne3);
+    r->op_params[0] = (int32_t) mode;
+    r->op = GGML_OP_UPSCALE;
+    r->src[0] = a;
+    return r;
+}
+struct ggml_tensor * ggml_upscale(struct ggml_context * ctx, struct ggml_tensor * a, int scale_factor, enum ggml_scale_mode mode) {
+    LITE_ASSERT(scale_factor >= 1);
+    return ggml_interpolate(ctx, a, a->ne[0] * scale_factor, a->ne[1] * scale_factor, a->ne[2], a->ne[3], (uint32_t) mode);
+}
+
 // ------------------------------------------------------------------------------------------------ graphs
 struct ggml_cgraph * ggml_new_graph_custom(struct ggml_context * ctx, size_t size, bool) {
     ggml_cgraph * g = new ggml_cgraph();

@@ -149,6 +149,25 @@ struct ggml_tensor * ggml_rwkv_wkv7(struct ggml_context * ctx, struct ggml_tenso
                                     struct ggml_tensor * a, struct ggml_tensor * b, struct ggml_tensor * state);
 struct ggml_tensor * ggml_gated_linear_attn(struct ggml_context * ctx, struct ggml_tensor * k, struct ggml_tensor * v, struct ggml_tensor * q, struct ggml_tensor * g,
                                             struct ggml_tensor * state, float scale);
+/* vision / audio towers (ggml_conv_2d patch embeddings, Whisper-style ggml_conv_1d stems, pooled projectors; DESIGN.md §4m states the contracts) */
+enum ggml_op_pool { GGML_OP_POOL_MAX, GGML_OP_POOL_AVG, GGML_OP_POOL_COUNT };
+enum ggml_scale_mode { GGML_SCALE_MODE_NEAREST = 0, GGML_SCALE_MODE_BILINEAR = 1, GGML_SCALE_MODE_BICUBIC = 2 };
+enum ggml_scale_flag { GGML_SCALE_FLAG_ALIGN_CORNERS = 1 << 8 };
+/* a: the convolution kernel [KW, KH, IC, OC] (1-D: [KW, IC, OC]), read for its extents; b: the data f32 [IW, IH, IC, N] (1-D: [IW, IC, N])
+ * -> dst_type [IC * KH * KW, OW, OH, N] (1-D: [IC * KW, OW, N]); op_params {s0, s1, p0, p1, d0, d1, is_2D} */
+struct ggml_tensor * ggml_im2col(struct ggml_context * ctx, struct ggml_tensor * a, struct ggml_tensor * b, int s0, int s1, int p0, int p1, int d0, int d1, bool is_2D,
+                                 enum ggml_type dst_type);
+/* im2col in the kernel's type, MUL_MAT(im2col, kernel), reshaped: 1-D -> [OL, OC, N]; 2-D -> cont(permute(0, 1, 3, 2)) = [OW, OH, OC, N] */
+struct ggml_tensor * ggml_conv_1d(struct ggml_context * ctx, struct ggml_tensor * a, struct ggml_tensor * b, int s0, int p0, int d0);
+struct ggml_tensor * ggml_conv_2d(struct ggml_context * ctx, struct ggml_tensor * a, struct ggml_tensor * b, int s0, int s1, int p0, int p1, int d0, int d1);
+/* op_params {op, k0, s0, p0} -> [(W + 2 p0 - k0) / s0 + 1, ne1, ne2, ne3]; {op, k0, k1, s0, s1, p0, p1} -> [(W + 2 p0 - k0) / s0 + 1, (H + 2 p1 - k1) / s1 + 1, ne2, ne3] */
+struct ggml_tensor * ggml_pool_1d(struct ggml_context * ctx, struct ggml_tensor * a, enum ggml_op_pool op, int k0, int s0, int p0);
+struct ggml_tensor * ggml_pool_2d(struct ggml_context * ctx, struct ggml_tensor * a, enum ggml_op_pool op, int k0, int k1, int s0, int s1, float p0, float p1);
+/* zeros appended at the high end of every dimension; no op_params at this ABI snapshot */
+struct ggml_tensor * ggml_pad(struct ggml_context * ctx, struct ggml_tensor * a, int p0, int p1, int p2, int p3);
+/* mode: a ggml_scale_mode, optionally | GGML_SCALE_FLAG_ALIGN_CORNERS, in op_params[0]; ggml_upscale multiplies dims 0 and 1 by scale_factor */
+struct ggml_tensor * ggml_upscale(struct ggml_context * ctx, struct ggml_tensor * a, int scale_factor, enum ggml_scale_mode mode);
+struct ggml_tensor * ggml_interpolate(struct ggml_context * ctx, struct ggml_tensor * a, int64_t ne0, int64_t ne1, int64_t ne2, int64_t ne3, uint32_t mode);
 
 /* graphs */
 struct ggml_cgraph * ggml_new_graph(struct ggml_context * ctx);
