@@ -1138,6 +1138,7 @@ void launch_flash_attn_combine(hipStream_t s, int D, const float * ws, const flo
     if (D == 256) hipLaunchKernelGGL((k_fattn_combine<256>), g2, dim3(256), 0, s, ws, sinks, dst, geo);
     else if (D == 128) hipLaunchKernelGGL((k_fattn_combine<128>), g2, dim3(128), 0, s, ws, sinks, dst, geo);
     else if (D == 64) hipLaunchKernelGGL((k_fattn_combine<64>), g2, dim3(64), 0, s, ws, sinks, dst, geo);
+    else if (fattn_hd_size(D) && !q8_out) launch_fattn_combine_hd(s, D, ws, sinks, dst, n_q, n_head, n_batch, n_splits);  // (72 / 80 / 88 / 112: one form, the real D at run time)
     else { MI_ERR("launch_flash_attn_combine: no combine pass for head_dim %d", D); abort(); }
 }
 
@@ -1146,7 +1147,7 @@ bool fattn_prefers_lists(const tdesc & q, const tdesc * mask, int mask_sparse) {
     return on && mask != nullptr && q.ne[1] >= fattn_mma_min_q() && q.ne[1] <= 256 && mask_sparse != 0;
 }
 int fattn_pick_splits(const tdesc & q, const tdesc & k, const tdesc * mask, int mask_sparse) {
-    if (q.ne[1] >= fattn_mma_min_q() && (k.ne[0] == 64 || k.ne[0] == 128 || k.ne[0] == 256) && !fattn_prefers_lists(q, mask, mask_sparse)) return fattn_mma_pick_splits(q, k);  // (soft-capped / ALiBi batches fall back to the generic kernel with this count)
+    if (q.ne[1] >= fattn_mma_min_q() && (k.ne[0] == 64 || k.ne[0] == 128 || k.ne[0] == 256 || fattn_hd_size(k.ne[0])) && !fattn_prefers_lists(q, mask, mask_sparse)) return fattn_mma_pick_splits(q, k);  // (soft-capped / ALiBi batches fall back to the generic kernel with this count)
     const int64_t n_kv = k.ne[1];
     if (q.ne[1] > 1 && (k.ne[0] == 128 || (k.ne[0] == 64 && k.type == GGML_TYPE_F16 && k.ne[2] > 0 && q.ne[2] % k.ne[2] == 0 && fa_g_ok(q.ne[2] / k.ne[2]))) && q.ne[3] == 1) {
         // a few tokens at head_dim 128 (continuous-batching decode, speculative batches): the tile-list kernel — every split takes a
@@ -1331,6 +1332,10 @@ void launch_flash_attn(hipStream_t s, const tdesc & q, const tdesc & k, const td
                        const fattn_params & p, void * workspace) {
     const bool q8 = p.kv_type == GGML_TYPE_Q8_0;
     if (!q8 && !p.dq && !p.lists && launch_flash_attn_mma(s, q, k, v, mask, sinks, dst, p, workspace)) return;  // (lists set: the caller chose the position-list form)
+    if (fattn_hd_size(k.ne[0])) {  // head sizes 72 / 80 / 88 / 112 below the matrix cores' batch, or in a form they do not take: fattn_hd.hip
+        launch_flash_attn_hd(s, q, k, v, mask, sinks, dst, p, workspace);
+        return;
+    }
     if (fattn_q8_via_f16(q, p.kv_type) && k.ne[3] == 1 && v.ne[3] == 1 && flash_attn_mma_applies(q, k, mask, sinks, dst, p)) {
         // a prompt batch over the quantised cache: the CPU quantises each query row to Q8_0 and takes integer block dots; here
         // the cells are expanded to f16 once (exact up to the f16 rounding of d * q) and the f16 matrix-core kernel runs on

@@ -909,8 +909,9 @@ int fattn_mma_min_q() {
 }
 bool flash_attn_mma_applies(const tdesc & q, const tdesc & k, const tdesc * mask, const float * sinks, const tdesc & dst, const fattn_params & p) {
     const int D = (int) k.ne[0];
-    if (q.ne[1] < fattn_mma_min_q() || sinks != nullptr || p.max_bias != 0.0f || (D != 64 && D != 128 && D != 256)) return false;
+    if (q.ne[1] < fattn_mma_min_q() || sinks != nullptr || p.max_bias != 0.0f || (D != 64 && D != 128 && D != 256 && !fattn_hd_size(D))) return false;
     if (p.logit_softcap != 0.0f && D != 256) return false;  // (soft-capped batches at 64 / 128 keep the generic kernel; at 256 — Gemma-2 caps every node — the CAP forms)
+    if (fattn_hd_size(D) && (k.type != GGML_TYPE_F16 || p.kv_type != GGML_TYPE_F16)) return false;  // (72 / 80 / 88 / 112, fattn_hd.hip: an f16 cache read in place)
     if ((k.ne[1] % 4) != 0 || (q.nb[1] % 16) || (q.nb[2] % 16) || (((uintptr_t) q.data) & 15) || (dst.nb[1] % 16) || (dst.nb[2] % 16) || (((uintptr_t) dst.data) & 15)) return false;
     if (mask && ((mask->nb[1] % 8) || (((uintptr_t) mask->data) & 7))) return false;
     return true;
@@ -946,7 +947,10 @@ bool launch_flash_attn_mma(hipStream_t s, const tdesc & q, const tdesc & k, cons
     const uint8_t * const tile_vis = tps <= 16384 ? p.tile_vis : nullptr;  // (without the states every tile is multiplied and reads its mask: correct, slower)
     const size_t vt_bytes = tile_vis ? (size_t) ((tps + 15) & ~15) : 0;  // the split's tile states (a byte per tile)
     g_fa_form = fa_form_code(FA_FORM_K_MMA, tile_vis ? 1 : 0, nw, FA_FORM_KV_F16, D, FA_FORM_TAIL_NONE);  // (the combine pass adds which kernel merges)
-    if (D == 256) {
+    if (fattn_hd_size(D)) {  // the padded forms: 96 columns for 72 / 80 / 88, 128 for 112
+        g_fa_form |= fa_form_hd(D);
+        launch_fattn_mma_hd(s, grid, nw, vt_bytes, q, k, v, mk, dst, mask != nullptr, geo.scale, geo.n_splits, ws, tile_vis);
+    } else if (D == 256) {
         if (nw == 4) { if (cap) launch_mma_d256<4, true>(s, grid, vt_bytes, q, k, v, mk, dst, geo, ws, tile_vis); else launch_mma_d256<4, false>(s, grid, vt_bytes, q, k, v, mk, dst, geo, ws, tile_vis); }
         else { if (cap) launch_mma_d256<2, true>(s, grid, vt_bytes, q, k, v, mk, dst, geo, ws, tile_vis); else launch_mma_d256<2, false>(s, grid, vt_bytes, q, k, v, mk, dst, geo, ws, tile_vis); }
     } else if (D == 128) {

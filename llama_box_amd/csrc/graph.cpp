@@ -214,7 +214,9 @@ bool mm_batched_q_ok(const ggml_tensor * op) {
 
 // which attention path serves this FLASH_ATTN_EXT node: 0 none (the host keeps it on the CPU backend), 1 the f16 kernels on the cache views in place,
 // 2 the lane-parallel kernel on block_q8_0 K / V, 3 the f16 kernels on an f16 IMAGE of whichever of K / V is kept in another type (kv_types.hip:
-// -ctk / -ctv q4_0, q4_1, q5_0, q5_1, iq4_nl, bf16, f32, mixed pairs, and q8_0 shapes route 2 does not take).  Head sizes 64, 128 and 256.
+// -ctk / -ctv q4_0, q4_1, q5_0, q5_1, iq4_nl, bf16, f32, mixed pairs, and q8_0 shapes route 2 does not take).  Head sizes 64, 128 and 256; 72, 80, 88 and 112 on
+// route 1 only (fattn_hd.hip: none of them is a whole number of 32-value blocks, so llama.cpp offers no block-format cache there; bf16 / f32 stay refused).
+// 96 stays refused: its refusal is pinned by a test.
 static int fa_route(const ggml_tensor * op) {
     const ggml_tensor * a = op->src[0];
     const ggml_tensor * k = op->src[1];
@@ -231,7 +233,9 @@ static int fa_route(const ggml_tensor * op) {
     }
     const bool k16 = k->type == GGML_TYPE_F16, v16 = v->type == GGML_TYPE_F16;
     if (!(k16 || kv_image_type(k->type)) || !(v16 || kv_image_type(v->type))) return 0;
-    if (k->ne[0] != v->ne[0] || (k->ne[0] != 64 && k->ne[0] != 128 && k->ne[0] != 256)) return 0;  // (256: Gemma; a q8_0 pair of that size lands here too — route 2 is head size 128 only)
+    const bool hd = fattn_hd_size(k->ne[0]);  // (72 / 80 / 88 / 112: vision towers, Phi-2, StableLM)
+    if (hd && !(k16 && v16)) return 0;
+    if (k->ne[0] != v->ne[0] || (k->ne[0] != 64 && k->ne[0] != 128 && k->ne[0] != 256 && !hd)) return 0;  // (256: Gemma; a q8_0 pair of that size lands here too — route 2 is head size 128 only)
     if (a->nb[0] != 4) return 0;
     for (const ggml_tensor * t : {k, v}) {
         if (t->type == GGML_TYPE_F16) {

@@ -406,7 +406,8 @@ void launch_flash_attn_combine(hipStream_t s, int D, const float * ws, const flo
 // FLASH_ATTN_EXT node's launch and copies it into that backend's stats behind it — the combine pass of the non-flash chain writes the thread's note too, which
 // nobody copies.  The stat is 0 for a graph without such a node; a replayed hipGraph reports what its capture walk noted.
 //   bits 0..3 kernel, 4..5 mode, 6..9 waves per workgroup, 10..11 cache kind, bit 12 head size 128 (clear: 64), bits 13..15 what merges the split records,
-//   bit 16 head size 256 (bit 12 is clear then; every code of a head-size-64 / -128 form keeps the value it had before that bit existed)
+//   bit 16 head size 256 (bit 12 is clear then; every code of a head-size-64 / -128 form keeps the value it had before that bit existed),
+//   bits 17..19 the padded-row head sizes of fattn_hd.hip (FA_FORM_HD_*; bits 12 and 16 are clear then; 0 for every other size: no earlier code moves)
 // (tests/fa_ref.py parses these names and values)
 enum {
     FA_FORM_K_SPLIT = 1, FA_FORM_K_DEC = 2, FA_FORM_K_MMA = 3,                                    // k_fattn_split / k_fattn_dec128 / k_fattn_mma
@@ -414,12 +415,22 @@ enum {
     FA_FORM_KV_F16 = 0, FA_FORM_KV_Q8_0 = 1, FA_FORM_KV_BLOCK = 2, FA_FORM_KV_Q8_IMAGE = 3,       // f16 cache, block_q8_0 in place, another block format in place, q8_0 through its f16 image
     FA_FORM_TAIL_NONE = 0, FA_FORM_TAIL_COMBINE = 1, FA_FORM_TAIL_COMBINE_ROWS = 2, FA_FORM_TAIL_SELF_MERGE = 3, FA_FORM_TAIL_MERGE2 = 4, FA_FORM_TAIL_FAT = 5,
     FA_FORM_D256_BIT = 16,  // the bit (not a field value) that says head size 256
+    FA_FORM_HD_SHIFT = 17,  // the field (bits 17..19) that names a padded-row head size; its values:
+    FA_FORM_HD_72 = 1, FA_FORM_HD_80 = 2, FA_FORM_HD_88 = 3, FA_FORM_HD_112 = 4,  // (5 is kept for 96, refused today: DESIGN.md §8)
 };
 static inline int fa_form_code(int kernel, int mode, int waves, int kv, int D, int tail) {
     if (D == 256) kernel |= 1 << FA_FORM_D256_BIT;
     return kernel | (mode << 4) | (waves << 6) | (kv << 10) | ((D == 128 ? 1 : 0) << 12) | (tail << 13);
 }
 extern thread_local int g_fa_form;  // (fattn.hip)
+// ---- head sizes 72 / 80 / 88 / 112 (fattn_hd.hip): a row on 16 lanes of which D / 8 are live; the matrix cores at the padded size 96 / 128.  f16 K / V only.
+static inline bool fattn_hd_size(int64_t D) { return D == 72 || D == 80 || D == 88 || D == 112; }
+// the head-size field a launcher ORs onto the head-size-64 code of its form (fa_form_tail leaves it alone: it rewrites bits 13..15)
+static inline int fa_form_hd(int64_t D) { return (D == 72 ? FA_FORM_HD_72 : D == 80 ? FA_FORM_HD_80 : D == 88 ? FA_FORM_HD_88 : D == 112 ? FA_FORM_HD_112 : 0) << FA_FORM_HD_SHIFT; }
+void launch_flash_attn_hd(hipStream_t s, const tdesc & q, const tdesc & k, const tdesc & v, const tdesc * mask, const float * sinks, const tdesc & dst, const fattn_params & p, void * workspace);
+void launch_fattn_combine_hd(hipStream_t s, int D, const float * ws, const float * sinks, const tdesc & dst, int n_q, int n_head, int n_batch, int n_splits);
+void launch_fattn_mma_hd(hipStream_t s, const dim3 grid, int nw, size_t vt_bytes, const tdesc & q, const tdesc & k, const tdesc & v, const tdesc & mk, const tdesc & dst, bool has_mask, float scale,
+                         int n_splits, float * ws, const uint8_t * tile_vis);
 
 // ---- the decode copy (repack.hip): rows [r0, r0 + n_rows) of a K-quant [K, N] matrix from the block layout at `src` into the plane layout at `dst` (same row stride)
 bool repack_supported(int type, int64_t K, int64_t nb1);
@@ -480,6 +491,7 @@ void tu_touch_ops(hipStream_t s);
 void tu_touch_ops_act(hipStream_t s);
 void tu_touch_fattn(hipStream_t s);
 void tu_touch_fattn_mma(hipStream_t s);
+void tu_touch_fattn_hd(hipStream_t s);
 void tu_touch_tp_p2p(hipStream_t s);
 void tu_touch_kv_types(hipStream_t s);
 void tu_touch_repack(hipStream_t s);
@@ -507,6 +519,7 @@ inline void preload_kernel_files(hipStream_t s) {
     tu_touch_ops_act(s);
     tu_touch_fattn(s);
     tu_touch_fattn_mma(s);
+    tu_touch_fattn_hd(s);
     tu_touch_tp_p2p(s);
     tu_touch_ssm(s);
     tu_touch_rwkv(s);
