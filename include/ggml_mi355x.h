@@ -100,6 +100,7 @@ typedef int64_t (*ggml_backend_mi355x_decode_copy_read_t)(ggml_backend_t backend
  * environment variables that set the same things): "graphs", "fusion", "prologue", "qkv", "mm_merge", "mmq_i8", "mmq_bn",
  * "mmq_skinny", "skinny_rope", "softmax_mm", "attn_nf", "mmq_min_cols", "mmvq_max_cols", "fa_splits", "fa_wo", "fa_self_merge", "small_uploads", "small_downloads",
  * "exec_update", "shadow_capture", "decode_copy" (the K-quants' plane copy and the Q8_0 panel copy), "decode_copy_headroom_gib", "q80_min_cols", "timing", "tp_p2p", "tp_p2p_reset" (forget an all-reduce time-out: every rank, all idle), "clear_failure" (forget a remembered HIP failure of a status-less entry point), "ssm_fuse" (SSM_CONV -> ADD -> SILU as one launch), "conv_mma" (MUL_MAT f16 x f16, the product behind an IM2COL: 0 dot form, 1 routed, 2 matrix cores wherever the operands allow),
+ * "gn_form" (GROUP_NORM: 0 routed by the group's length, 1 the resident form wherever a group fits it, 2 the split form everywhere; GGML_MI355X_GN_FORM),
  * "mmid_bias" (an ADD_ID directly behind its MUL_MAT_ID — the per-expert bias of a gpt-oss expert block — rides in that launch's store; default 1, GGML_MI355X_MMID_BIAS). */
 typedef int (*ggml_backend_mi355x_set_option_t)(ggml_backend_t backend, const char * key, const char * value);
 /* Counters for tests/bench: "graph_launches", "graph_captures", "graph_early_captures", "graph_shadow_captures", "graph_capture_walk_ns", "graph_exec_update_ns", "graph_shadow_eager_ns", "graph_exec_updates", "eager_graphs", "kernel_launches", "fused_nodes",

@@ -143,6 +143,8 @@ _SIGS = {
     "ggml_im2col": (TP, [_P, TP, TP, _I, _I, _I, _I, _I, _I, _B, _I]), "ggml_conv_1d": (TP, [_P, TP, TP, _I, _I, _I]), "ggml_conv_2d": (TP, [_P, TP, TP, _I, _I, _I, _I, _I, _I]),
     "ggml_pool_1d": (TP, [_P, TP, _I, _I, _I, _I]), "ggml_pool_2d": (TP, [_P, TP, _I, _I, _I, _I, _I, _F, _F]), "ggml_pad": (TP, [_P, TP, _I, _I, _I, _I]),
     "ggml_upscale": (TP, [_P, TP, _I, _I]), "ggml_interpolate": (TP, [_P, TP, _I64, _I64, _I64, _I64, C.c_uint32]),
+    "ggml_group_norm": (TP, [_P, TP, _I, _F]), "ggml_group_norm_inplace": (TP, [_P, TP, _I, _F]), "ggml_timestep_embedding": (TP, [_P, TP, _I, _I]),
+    "ggml_diag_mask_inf": (TP, [_P, TP, _I]), "ggml_diag_mask_inf_inplace": (TP, [_P, TP, _I]), "ggml_leaky_relu": (TP, [_P, TP, _F, _B]),
     "ggml_new_graph": (C.POINTER(CGraph), [_P]), "ggml_new_graph_custom": (C.POINTER(CGraph), [_P, _SZ, _B]),
     "ggml_build_forward_expand": (None, [C.POINTER(CGraph), TP]), "ggml_graph_n_nodes": (_I, [C.POINTER(CGraph)]),
     "ggml_graph_node": (TP, [C.POINTER(CGraph), _I]), "ggml_graph_view": (CGraph, [C.POINTER(CGraph), _I, _I]),

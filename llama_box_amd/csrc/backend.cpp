@@ -727,6 +727,7 @@ static ggml_backend_t dev_init_backend(ggml_backend_dev_t dev, const char *) {
     c->ssm_fuse = env_flag("GGML_MI355X_SSM_FUSE", true);
     c->mmid_bias = env_flag("GGML_MI355X_MMID_BIAS", true);
     c->conv_mma = std::max(0, std::min(2, env_int("GGML_MI355X_CONV_MMA", 1)));
+    c->gn_form = std::max(0, std::min(2, env_int("GGML_MI355X_GN_FORM", 0)));
     if (hipMalloc((void **) &c->ss_buf, 256 * sizeof(double)) != hipSuccess) {  // (optional: without it every norm prologue sums its own row)
         (void) hipGetLastError();
         c->ss_buf = nullptr;
@@ -832,6 +833,7 @@ static int api_set_option(ggml_backend_t be, const char * key, const char * valu
         else if (k == "ssm_fuse") c->ssm_fuse = v != 0;
         else if (k == "mmid_bias") c->mmid_bias = v != 0;
         else if (k == "conv_mma") { if (v < 0 || v > 2) return -2; c->conv_mma = v; }
+        else if (k == "gn_form") { if (v < 0 || v > 2) return -2; c->gn_form = v; }
         else return -1;
     }
     HIP_SOFT(hipStreamSynchronize(c->stream));

@@ -159,6 +159,7 @@ struct backend_ctx {
     bool capturing = false;
     bool ssm_fuse = true;      // SSM_CONV -> ADD(bias) -> SILU as one launch (set_option "ssm_fuse" / GGML_MI355X_SSM_FUSE; options.h says why it is no row of MI_OPTIONS)
     int conv_mma = 1;          // MUL_MAT f16 x f16 (the product behind an IM2COL): 1 = the matrix cores where the shape is routed there, 0 = the dot form everywhere, 2 = the matrix cores wherever the operands allow (set_option "conv_mma" / GGML_MI355X_CONV_MMA; beside the table as ssm_fuse is)
+    int gn_form = 0;           // GROUP_NORM: 0 = routed (diffusion.hip: group_norm_runs_resident), 1 = the resident form wherever a group fits it, 2 = the split form everywhere (set_option "gn_form" / GGML_MI355X_GN_FORM; beside the table as ssm_fuse is)
     bool mmid_bias = true;     // MUL_MAT_ID -> ADD_ID as one launch, the bias in the store (set_option "mmid_bias" / GGML_MI355X_MMID_BIAS; kept beside the table as ssm_fuse is)
     bool mm_q5_major = false;  // the graph being planned / run holds more Q5_K than Q4_K weight bytes (graph.cpp: mmq_min_cols_for)
     // tensor parallel

@@ -468,6 +468,49 @@ static bool upscale_ok(const ggml_tensor * op) {
     return true;
 }
 
+// The ops the image-generation graphs add (diffusion.hip; DESIGN.md §4n restates their contracts).  Shapes, types and strides only; whatever is outside the stated
+// contract is refused.
+// GROUP_NORM {n_groups, eps}: f32, source and result contiguous and of one shape [W, H, C, N], the result apart from the source or the source itself (the _inplace
+// form).  cpg = ceil(C / G); a node whose last group would be empty, (G - 1) cpg >= C, is refused (ggml-cpu divides by a non-positive count there).  A group is
+// shorter than 2^31 values (the kernels' 32-bit channel arithmetic) and G * N fits a grid's y extent
+static bool group_norm_ok(const ggml_tensor * op) {
+    const ggml_tensor * a = op->src[0];
+    if (!a || !is_f32_contig(a) || !is_f32_contig(op) || !same_shape(a, op)) return false;
+    const int64_t G = op->op_params[0], C = a->ne[2];
+    for (int d = 0; d < 4; ++d) if (a->ne[d] < 1) return false;
+    if (G <= 0 || G > C) return false;
+    const int64_t cpg = (C + G - 1) / G;
+    if ((G - 1) * cpg >= C || G * a->ne[3] > 65535) return false;
+    if (a->ne[0] * a->ne[1] >= ((int64_t) 1 << 31) / cpg) return false;
+    return !ranges_overlap(op, a) || op->data == a->data;
+}
+// TIMESTEP_EMBEDDING {dim, max_period}: timesteps f32 contiguous [N] -> f32 contiguous [dim rounded up to even, N]; dim >= 2, max_period >= 1
+static bool timestep_embedding_ok(const ggml_tensor * op) {
+    const ggml_tensor * a = op->src[0];
+    if (!a || !is_f32_contig(a) || !is_f32_contig(op) || a->ne[0] < 1 || a->ne[1] != 1 || a->ne[2] != 1 || a->ne[3] != 1) return false;
+    const int64_t dim = op->op_params[0];
+    if (dim < 2 || op->op_params[1] < 1 || a->ne[0] > CONV_MAX_ELEMS / (dim + 1)) return false;
+    return op->ne[0] == dim + (dim & 1) && op->ne[1] == a->ne[0] && op->ne[2] == 1 && op->ne[3] == 1;
+}
+// DIAG_MASK_INF {n_past}: f32 with contiguous rows on both sides, every other stride a multiple of 4, one shape, n_past >= 0; the result apart from the source, or the
+// _inplace form: a view of the source with the source's address and strides.  DIAG_MASK_ZERO is no case of supports_op
+static bool diag_mask_inf_ok(const ggml_tensor * op) {
+    const ggml_tensor * a = op->src[0];
+    if (!a || a->type != GGML_TYPE_F32 || op->type != GGML_TYPE_F32 || !same_shape(a, op) || a->nb[0] != 4 || op->nb[0] != 4 || op->op_params[0] < 0) return false;
+    if (ggml_abi_nelements(op) > CONV_MAX_ELEMS) return false;
+    bool same_layout = op->data == a->data;
+    for (int d = 0; d < 4; ++d) {
+        if (a->ne[d] < 1 || (a->nb[d] % 4) || (op->nb[d] % 4)) return false;
+        same_layout = same_layout && a->nb[d] == op->nb[d];
+    }
+    return !ranges_overlap(op, a) || same_layout;
+}
+// LEAKY_RELU {slope as f32}: f32 contiguous on both sides, one shape; the result may be the source
+static bool leaky_relu_ok(const ggml_tensor * op) {
+    const ggml_tensor * a = op->src[0];
+    return a && is_f32_contig(a) && is_f32_contig(op) && same_shape(a, op) && (!ranges_overlap(op, a) || op->data == a->data);
+}
+
 bool supports_op(const ggml_tensor * op) {
     const ggml_tensor * a = op->src[0];
     const ggml_tensor * b = op->src[1];
@@ -584,6 +627,14 @@ bool supports_op(const ggml_tensor * op) {
             return pad_ok(op);
         case GGML_OP_UPSCALE:
             return upscale_ok(op);
+        case GGML_OP_GROUP_NORM:
+            return group_norm_ok(op);
+        case GGML_OP_TIMESTEP_EMBEDDING:
+            return timestep_embedding_ok(op);
+        case GGML_OP_DIAG_MASK_INF:
+            return diag_mask_inf_ok(op);
+        case GGML_OP_LEAKY_RELU:
+            return leaky_relu_ok(op);
         default:
             return false;
     }
@@ -667,6 +718,9 @@ static ws_plan plan_ws(backend_ctx * c, const ggml_cgraph * g) {
                 continue;
             }
             p.aux_bytes = std::max(p.aux_bytes, fattn_workspace_bytes(q, k, v, ns, n->src[1]->type));
+        } else if (n->op == GGML_OP_GROUP_NORM && group_norm_ok(n)) {
+            // the split form's partial sums (16 bytes a chunk), planned whatever form the node takes: a captured graph never grows the scratch
+            p.aux_bytes = std::max(p.aux_bytes, group_norm_scratch_bytes(TD(n->src[0]), n->op_params[0]));
         }
     }
     p.act_bytes = (p.act_bytes + 255) & ~(size_t) 255;
@@ -1214,6 +1268,51 @@ static norm_affine find_norm_affine(const exec_state & st, int i) {
         const ggml_tensor * v = t->src[0] == cur ? t->src[1] : (t->src[1] == cur ? t->src[0] : nullptr);
         if (!row_vector(v)) break;
         (k == 1 ? f.w : f.b) = v;
+        f.out = cur = t;
+        f.absorbed = k;
+    }
+    return f;
+}
+
+// GROUP_NORM n (node i) -> MUL(n, w) -> ADD(., b) -> UNARY(SILU): a ResBlock's / attention block's norm in the UNet and the VAE (sd.cpp: GroupNorm32 followed by
+// ggml_silu_inplace).  The writing pass of either form applies `* w[c]`, `+ b[c]` and silu_f itself and writes the last absorbed node's tensor; the longest prefix
+// of the chain that passes the guards is absorbed.  The guards are find_norm_affine's: each absorbed result has one reader and is no output, w and b are f32,
+// contiguous, [1, 1, C, 1], the shape is kept, the result is f32 and contiguous, and the memory written (a LATER node's, which the host allocator may have cut out
+// of a recycled block) is the source itself or apart from everything the launch reads.
+struct group_norm_affine {
+    const ggml_tensor * w = nullptr;
+    const ggml_tensor * b = nullptr;
+    bool silu = false;
+    const ggml_tensor * out = nullptr;  // the tensor the launch writes: n, the MUL, the ADD or the UNARY
+    int absorbed = 0;                   // nodes behind n that the launch stands for: 0 .. 3
+};
+static group_norm_affine find_group_norm_affine(const exec_state & st, int i) {
+    const ggml_cgraph * g = st.g;
+    const ggml_tensor * n = g->nodes[i];
+    const ggml_tensor * x = n->src[0];
+    group_norm_affine f;
+    f.out = n;
+    auto channel_vector = [&](const ggml_tensor * v) {
+        return v && v->type == GGML_TYPE_F32 && ggml_abi_is_contiguous(v) && v->ne[0] == 1 && v->ne[1] == 1 && v->ne[2] == n->ne[2] && v->ne[3] == 1;
+    };
+    auto dst_ok = [&](const ggml_tensor * d) {
+        if (!is_f32_contig(d) || !same_shape(d, n)) return false;
+        if (ranges_overlap(d, x) && d->data != x->data) return false;
+        return !(f.w && ranges_overlap(d, f.w)) && !(f.b && ranges_overlap(d, f.b));
+    };
+    const ggml_tensor * cur = n;
+    for (int k = 1; k <= 3 && i + k < g->n_nodes; ++k) {
+        const ggml_tensor * t = g->nodes[i + k];
+        if (st.done[i + k] || !single_use(st, cur)) break;
+        if (k == 3) {
+            if (t->op != GGML_OP_UNARY || t->op_params[0] != GGML_UNARY_OP_SILU || t->src[0] != cur || !dst_ok(t)) break;
+            f.silu = true;
+        } else {
+            if (t->op != (k == 1 ? GGML_OP_MUL : GGML_OP_ADD) || t->src[0] != cur || !channel_vector(t->src[1])) break;
+            const ggml_tensor * v = t->src[1];
+            if (ranges_overlap(t, v) || (f.w && ranges_overlap(t, f.w)) || !dst_ok(t)) break;
+            (k == 1 ? f.w : f.b) = v;
+        }
         f.out = cur = t;
         f.absorbed = k;
     }
@@ -2468,8 +2567,10 @@ static int run_node(exec_state & st, int i) {
             if (is_gelu_op(n->op_params[0])) {
                 timed_scope ts(c, "gelu", (double) ggml_abi_nbytes(n) * 2);
                 if (!launch_gelu(s, n->op_params[0], TD(a), TD(n), c->act_tab)) return -1;
-            } else
-            launch_unary(s, n->op_params[0], TD(a), TD(n));
+            } else {
+                timed_scope ts(c, "unary", (double) ggml_abi_nbytes(n) * 2);
+                launch_unary(s, n->op_params[0], TD(a), TD(n));
+            }
             c->st.kernel_launches++;
             return 1;
         case GGML_OP_GLU: {
@@ -2875,6 +2976,37 @@ static int run_node(exec_state & st, int i) {
         case GGML_OP_UPSCALE:
             if (!upscale_ok(n)) { MI_ERR("graph_compute: node %d '%s' is outside UPSCALE's contract (DESIGN.md 4m)", i, n->name); return -1; }
             if (!launch_upscale(s, TD(a), TD(n), n->op_params[0])) return -1;
+            c->st.kernel_launches++;
+            return 1;
+        case GGML_OP_GROUP_NORM: {
+            // GROUP_NORM -> MUL(., w) -> ADD(., b) -> SILU: one launch (resident) or the last of three (split) writing the last absorbed node's output
+            if (!group_norm_ok(n)) { MI_ERR("graph_compute: node %d '%s' is outside GROUP_NORM's contract (DESIGN.md 4n)", i, n->name); return -1; }
+            group_norm_affine f;
+            f.out = n;
+            if (fuse) f = find_group_norm_affine(st, i);
+            const tdesc ta = TD(a);
+            const bool resident = group_norm_runs_resident(ta, n->op_params[0], c->gn_form);
+            timed_scope ts(c, resident ? (f.absorbed ? "group_norm_res_affine" : "group_norm_res") : (f.absorbed ? "group_norm_split_affine" : "group_norm_split"), (double) ggml_abi_nbytes(a) * 2);
+            if (!launch_group_norm(s, ta, TD(f.out), n->op_params[0], ggml_abi_op_param_f32(n, 1), f.w ? (const float *) f.w->data : nullptr, f.b ? (const float *) f.b->data : nullptr, f.silu,
+                                   c->gn_form, c->ws ? (char *) c->ws + st.aux_off : nullptr, c->ws ? c->ws_size - st.aux_off : 0))
+                return -1;
+            c->st.kernel_launches += resident ? 1 : 3;
+            c->st.fused_nodes += f.absorbed;
+            return 1 + f.absorbed;
+        }
+        case GGML_OP_TIMESTEP_EMBEDDING:
+            if (!timestep_embedding_ok(n)) { MI_ERR("graph_compute: node %d '%s' is outside TIMESTEP_EMBEDDING's contract (DESIGN.md 4n)", i, n->name); return -1; }
+            launch_timestep_embedding(s, TD(a), TD(n), n->op_params[0], n->op_params[1]);
+            c->st.kernel_launches++;
+            return 1;
+        case GGML_OP_DIAG_MASK_INF:
+            if (!diag_mask_inf_ok(n)) { MI_ERR("graph_compute: node %d '%s' is outside DIAG_MASK_INF's contract (DESIGN.md 4n)", i, n->name); return -1; }
+            launch_diag_mask_inf(s, TD(a), TD(n), n->op_params[0]);
+            c->st.kernel_launches++;
+            return 1;
+        case GGML_OP_LEAKY_RELU:
+            if (!leaky_relu_ok(n)) { MI_ERR("graph_compute: node %d '%s' is outside LEAKY_RELU's contract (DESIGN.md 4n)", i, n->name); return -1; }
+            launch_leaky_relu(s, TD(a), TD(n), ggml_abi_op_param_f32(n, 0));
             c->st.kernel_launches++;
             return 1;
         default:

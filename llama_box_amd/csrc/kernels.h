@@ -471,6 +471,29 @@ bool launch_pool(hipStream_t s, const tdesc & src, const tdesc & dst, const int3
 void launch_pad(hipStream_t s, const tdesc & src, const tdesc & dst);
 bool launch_upscale(hipStream_t s, const tdesc & src, const tdesc & dst, int mode);
 
+// ---- image generation (diffusion.hip; DESIGN.md 4n states the contracts, graph.cpp's group_norm_ok / timestep_embedding_ok / diag_mask_inf_ok / leaky_relu_ok check them)
+// GROUP_NORM: src / dst f32 contiguous [W, H, C, N], dst apart from src or src itself; mul_w / add_b (C floats each) and silu: the MUL, ADD and UNARY(SILU) nodes the
+// writing pass stands for (add_b needs mul_w, silu needs both).  Two forms (diffusion.hip says how each works); group_norm_runs_resident is THE form choice, form
+// being the gn_form switch (0 routed, 1 resident wherever a full group fits, 2 split everywhere):
+//   MI_GN_RESIDENT_MAX  values of the largest group the resident form holds: 1024 threads x 40 registers
+//   MI_GN_CHUNK         values of one chunk of the split form (a source constant: the partial sums' order, hence the bits, depend on it)
+//   MI_GN_ROUTED_MAX    routed (gn_form 0): resident up to this many values a full group, split above.  Measured on the MI355X with the chain an SD graph runs,
+//                       GROUP_NORM -> MUL -> ADD -> SILU fused, 32 groups (scripts/ubench/diffusion_bench.py, profiles/diffusion_ubench.txt): resident / split
+//                       7.8 / 15.5 us at 2 560 values, 10.5 / 17.3 at 10 240, 17.5 / 17.7 at 20 480 (a tie inside the spreads), 26.0 / 19.1 at 40 960: 32 workgroups
+//                       doing the affine and silu_f of 160 KB each lose to 320 chunks.  (GROUP_NORM alone: 11.9 / 14.9 at 40 960 — resident wins, by less)
+#define MI_GN_RESIDENT_MAX 40960
+#define MI_GN_CHUNK 4096
+#define MI_GN_ROUTED_MAX 20480
+bool group_norm_runs_resident(const tdesc & src, int n_groups, int form);
+size_t group_norm_scratch_bytes(const tdesc & src, int n_groups);  // the split form's partial sums (plan_ws: aux_bytes)
+bool launch_group_norm(hipStream_t s, const tdesc & src, const tdesc & dst, int n_groups, float eps, const float * mul_w, const float * add_b, bool silu, int form, void * scratch,
+                       size_t scratch_bytes);
+// TIMESTEP_EMBEDDING: timesteps f32 [N] -> dst f32 [dim rounded up to even, N]; DIAG_MASK_INF: rows contiguous, in place when dst.data == src.data (only masked cells are
+// written); LEAKY_RELU: f32 contiguous, dst may be src
+void launch_timestep_embedding(hipStream_t s, const tdesc & timesteps, const tdesc & dst, int dim, int max_period);
+void launch_diag_mask_inf(hipStream_t s, const tdesc & src, const tdesc & dst, int n_past);
+void launch_leaky_relu(hipStream_t s, const tdesc & src, const tdesc & dst, float slope);
+
 // ---- code-object preload (round 4).  The HIP runtime loads a translation unit's device code on the FIRST launch of one of its kernels
 // (0.3 - 2 ms each, measured as idle gaps in front of the first prompt's kernels: 5.5 ms of a 64 ms prefill).  Every kernel file ends with
 // MI_TU_TOUCH(name): an empty kernel + a launcher; init_backend launches them all once per device, so the cost moves to start-up.
@@ -500,6 +523,7 @@ void tu_touch_mmb(hipStream_t s);
 void tu_touch_ssm(hipStream_t s);
 void tu_touch_rwkv(hipStream_t s);
 void tu_touch_conv(hipStream_t s);
+void tu_touch_diffusion(hipStream_t s);
 inline void preload_kernel_files(hipStream_t s) {
     tu_touch_kv_types(s);
     tu_touch_repack(s);
@@ -524,6 +548,7 @@ inline void preload_kernel_files(hipStream_t s) {
     tu_touch_ssm(s);
     tu_touch_rwkv(s);
     tu_touch_conv(s);
+    tu_touch_diffusion(s);
 }
 
 }  // namespace mi355x

@@ -66,6 +66,8 @@ namespace mi355x {
 // added in the store (graph.cpp, mmid.hip).
 // conv_mma (backend_ctx::conv_mma, default 1, GGML_MI355X_CONV_MMA, set_option("conv_mma", 0 / 1 / 2)) likewise: MUL_MAT f16 x f16, the product behind an IM2COL.
 // 1: on the matrix cores where the shape is routed there; 0: the dot form everywhere; 2: the matrix cores wherever the operands allow (A/B runs, tests; conv.hip).
+// gn_form (backend_ctx::gn_form, default 0, GGML_MI355X_GN_FORM, set_option("gn_form", 0 / 1 / 2)) likewise: which of GROUP_NORM's two forms serves a node.
+// 0: routed by the group's length; 1: the resident form wherever a group fits it; 2: the split form everywhere (A/B runs, tests; diffusion.hip).
 
 struct options {
 #define MI_X(type, name, def, flag, env) type name = def;

@@ -762,6 +762,8 @@ static bool analyse_node(analysis & A, const ggml_tensor * t) {
             return A.fail("an op of a linear-attention recurrent layer, which the engine has no rule for", t);  // (as it has none for the SSM ops)
         case GGML_OP_IM2COL: case GGML_OP_POOL_1D: case GGML_OP_POOL_2D: case GGML_OP_PAD: case GGML_OP_UPSCALE:
             return A.fail("an op of a vision / audio tower, which the engine has no rule for", t);  // (a tower runs on the one device its projector lives on)
+        case GGML_OP_GROUP_NORM: case GGML_OP_TIMESTEP_EMBEDDING: case GGML_OP_DIAG_MASK_INF: case GGML_OP_LEAKY_RELU:
+            return A.fail("an op of an image-generation graph, which the engine has no rule for", t);  // (the diffusion model, the VAE and CLIP each run on one device)
         default:
             return A.fail("an op the engine has no rule for", t);
     }

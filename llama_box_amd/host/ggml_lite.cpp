@@ -803,6 +803,43 @@ struct ggml_tensor * ggml_upscale(struct ggml_context * ctx, struct ggml_tensor 
     return ggml_interpolate(ctx, a, a->ne[0] * scale_factor, a->ne[1] * scale_factor, a->ne[2], a->ne[3], (uint32_t) mode);
 }
 
+// image generation (ggml.c: ggml_group_norm_impl, ggml_timestep_embedding, ggml_diag_mask_inf_impl, ggml_leaky_relu; DESIGN.md §4n states the contracts)
+static ggml_tensor * group_norm_impl(ggml_context * ctx, ggml_tensor * a, int n_groups, float eps, bool inplace) {
+    ggml_tensor * r = inplace ? view_tensor(ctx, a) : dup_tensor(ctx, a);
+    r->op_params[0] = n_groups;
+    set_f32(r, 1, eps);
+    r->op = GGML_OP_GROUP_NORM;
+    r->src[0] = a;
+    return r;
+}
+struct ggml_tensor * ggml_group_norm(struct ggml_context * ctx, struct ggml_tensor * a, int n_groups, float eps) { return group_norm_impl(ctx, a, n_groups, eps, false); }
+struct ggml_tensor * ggml_group_norm_inplace(struct ggml_context * ctx, struct ggml_tensor * a, int n_groups, float eps) { return group_norm_impl(ctx, a, n_groups, eps, true); }
+struct ggml_tensor * ggml_timestep_embedding(struct ggml_context * ctx, struct ggml_tensor * timesteps, int dim, int max_period) {
+    const int actual_dim = dim + (dim % 2 != 0 ? 1 : 0);
+    ggml_tensor * r = ggml_new_tensor_2d(ctx, GGML_TYPE_F32, actual_dim, timesteps->ne[0]);
+    r->op_params[0] = dim;
+    r->op_params[1] = max_period;
+    r->op = GGML_OP_TIMESTEP_EMBEDDING;
+    r->src[0] = timesteps;
+    return r;
+}
+static ggml_tensor * diag_mask_inf_impl(ggml_context * ctx, ggml_tensor * a, int n_past, bool inplace) {
+    ggml_tensor * r = inplace ? view_tensor(ctx, a) : dup_tensor(ctx, a);
+    r->op_params[0] = n_past;
+    r->op = GGML_OP_DIAG_MASK_INF;
+    r->src[0] = a;
+    return r;
+}
+struct ggml_tensor * ggml_diag_mask_inf(struct ggml_context * ctx, struct ggml_tensor * a, int n_past) { return diag_mask_inf_impl(ctx, a, n_past, false); }
+struct ggml_tensor * ggml_diag_mask_inf_inplace(struct ggml_context * ctx, struct ggml_tensor * a, int n_past) { return diag_mask_inf_impl(ctx, a, n_past, true); }
+struct ggml_tensor * ggml_leaky_relu(struct ggml_context * ctx, struct ggml_tensor * a, float negative_slope, bool inplace) {
+    ggml_tensor * r = inplace ? view_tensor(ctx, a) : dup_tensor(ctx, a);
+    set_f32(r, 0, negative_slope);
+    r->op = GGML_OP_LEAKY_RELU;
+    r->src[0] = a;
+    return r;
+}
+
 // ------------------------------------------------------------------------------------------------ graphs
 struct ggml_cgraph * ggml_new_graph_custom(struct ggml_context * ctx, size_t size, bool) {
     ggml_cgraph * g = new ggml_cgraph();

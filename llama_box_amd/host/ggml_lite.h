@@ -168,6 +168,17 @@ struct ggml_tensor * ggml_pad(struct ggml_context * ctx, struct ggml_tensor * a,
 /* mode: a ggml_scale_mode, optionally | GGML_SCALE_FLAG_ALIGN_CORNERS, in op_params[0]; ggml_upscale multiplies dims 0 and 1 by scale_factor */
 struct ggml_tensor * ggml_upscale(struct ggml_context * ctx, struct ggml_tensor * a, int scale_factor, enum ggml_scale_mode mode);
 struct ggml_tensor * ggml_interpolate(struct ggml_context * ctx, struct ggml_tensor * a, int64_t ne0, int64_t ne1, int64_t ne2, int64_t ne3, uint32_t mode);
+/* image generation (stable-diffusion.cpp's UNet, VAE, CLIP and ESRGAN graphs; DESIGN.md §4n states the contracts) */
+/* op_params {n_groups, eps as f32}; a [W, H, C, N]; the _inplace form is a view of a */
+struct ggml_tensor * ggml_group_norm(struct ggml_context * ctx, struct ggml_tensor * a, int n_groups, float eps);
+struct ggml_tensor * ggml_group_norm_inplace(struct ggml_context * ctx, struct ggml_tensor * a, int n_groups, float eps);
+/* op_params {dim, max_period}; timesteps f32 [N] -> f32 [dim rounded up to even, N] */
+struct ggml_tensor * ggml_timestep_embedding(struct ggml_context * ctx, struct ggml_tensor * timesteps, int dim, int max_period);
+/* op_params {n_past}; the _inplace form is a view of a */
+struct ggml_tensor * ggml_diag_mask_inf(struct ggml_context * ctx, struct ggml_tensor * a, int n_past);
+struct ggml_tensor * ggml_diag_mask_inf_inplace(struct ggml_context * ctx, struct ggml_tensor * a, int n_past);
+/* op_params {negative_slope as f32}; inplace: a view of a */
+struct ggml_tensor * ggml_leaky_relu(struct ggml_context * ctx, struct ggml_tensor * a, float negative_slope, bool inplace);
 
 /* graphs */
 struct ggml_cgraph * ggml_new_graph(struct ggml_context * ctx);
