@@ -67,6 +67,18 @@ __device__ __forceinline__ float wave_max(float v) {
     v = fmaxf(v, dpp_f32<MI_DPP_ROR1>(v));
     return fmaxf(fmaxf(readlane_f32(v, 0), readlane_f32(v, 16)), fmaxf(readlane_f32(v, 32), readlane_f32(v, 48)));
 }
+// element-wise all-reduce over the four 16-lane DPP rows of a wave (lane l ends with x[l&15] + x[16+(l&15)] + ...):
+// gfx950's v_permlane{16,32}_swap exchange odd/even rows (halves) of two registers, so two swaps and two adds do it
+// without touching LDS.  (Inline asm: with identical operands the builtin form folds to x + x in this compiler.)
+__device__ __forceinline__ float xrow_allsum(const float x) {
+    float a = x, b = x;
+    asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(a), "+v"(b));
+    float y = a + b;
+    a = y;
+    b = y;
+    asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(a), "+v"(b));
+    return a + b;
+}
 
 // IEEE binary16 <-> f32, round-to-nearest-even (v_cvt_f16_f32 / v_cvt_f32_f16), bit-identical to the CPU path
 __device__ __forceinline__ float h2f(uint16_t h) {

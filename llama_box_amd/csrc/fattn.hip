@@ -49,19 +49,7 @@ struct fa_geom {
                         // the last workgroup to arrive in ONE round trip of 8-byte agent-scope loads (MODE 0, f32 output, <= 32 splits, any wave count)
 };
 
-// element-wise all-reduce over the four 16-lane DPP rows of a wave (lane l ends with x[l&15] + x[16+(l&15)] + ...):
-// gfx950's v_permlane{16,32}_swap exchange odd/even rows (halves) of two registers, so two swaps and two adds do it
-// without touching LDS.  (Inline asm: with identical operands the builtin form folds to x + x in this compiler.)
-__device__ __forceinline__ float xrow_allsum(const float x) {
-    float a = x, b = x;
-    asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(a), "+v"(b));
-    float y = a + b;
-    a = y;
-    b = y;
-    asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(a), "+v"(b));
-    return a + b;
-}
-
+// (xrow_allsum, the all-reduce over the four 16-lane rows of a wave: dev_util.h)
 // (x.lo+x.hi | y.lo+y.hi): lanes 0-31 get the two-half total of x, lanes 32-63 that of y
 __device__ __forceinline__ float swap32_pairsum(float x, float y) {
     asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(x), "+v"(y));

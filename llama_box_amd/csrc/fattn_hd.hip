@@ -7,12 +7,9 @@
 //                         the 16-lane DPP sum of the dot and the element-wise sums of the accumulators are those of the live lanes.  The bytes behind a head's
 //                         row belong to the next head, the next cell or nobody: loading them and multiplying by a zero query is not the same thing (0 x NaN).
 //   k_fattn_combine_hd    the merge of the split records, a thread per real dimension.
-//   k_fattn_mma_hd<DP, NW> 33 tokens and more: k_fattn_mma computed at the padded size DP = 96 (72 / 80 / 88) or 128 (112).  The pad columns of the staged K tile
-//                         and the pad entries of the query fragments are WRITTEN as zeros and never loaded, so every padded product adds an exact zero; V is
-//                         staged for the real D / 8 chunks only (the pad rows of V^T are zeroed once: their output rows are never stored); output and record
-//                         stores skip the runs at d0 >= D.  72 and 88 end in a half-live k-step (8 of its 16 dims).
 //
-// D is a RUN-TIME value in all three (one instantiation per G, one per (DP, NW)): records, the cross-wave merge and the stores use the real D, stride D + 2.
+// 33 tokens and more run on the matrix cores: k_fattn_mma<96 | 128, NW, false, PAD = true> (fattn_mma.hip), the walk of the other head sizes at a padded column count.
+// D is a RUN-TIME value in all three (one instantiation per G, one per (padded size, NW)): records, the cross-wave merge and the stores use the real D, stride D + 2.
 // DESIGN.md §4d has the resource table, the timings and what was not chosen.
 #include <algorithm>
 #include <cmath>
@@ -27,17 +24,6 @@ struct fa_hd_geom {
     float scale, softcap, max_bias, m0, m1;
     uint32_t n_head_log2;
 };
-
-// element-wise all-reduce over the four 16-lane DPP rows of a wave (fattn.hip: xrow_allsum)
-static __device__ __forceinline__ float hd_xrow_allsum(const float x) {
-    float a = x, b = x;
-    asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(a), "+v"(b));
-    float y = a + b;
-    a = y;
-    b = y;
-    asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(a), "+v"(b));
-    return a + b;
-}
 
 #define FA_HD_SH 116  // floats per (wave, head) slot of the cross-wave merge: 112 values, max, sum, 2 pad (16-byte aligned rows)
 
@@ -164,9 +150,9 @@ __global__ void __launch_bounds__(256) k_fattn_split_hd(const tdesc q, const tde
     // rows of the wave share (m); their partial sums add up element-wise across the four sub-rows
 #pragma unroll
     for (int g = 0; g < G; ++g) {
-        l[g] = hd_xrow_allsum(l[g]);
+        l[g] = xrow_allsum(l[g]);
 #pragma unroll
-        for (int i = 0; i < 8; ++i) acc[g][i] = hd_xrow_allsum(acc[g][i]);
+        for (int i = 0; i < 8; ++i) acc[g][i] = xrow_allsum(acc[g][i]);
     }
     if (sub == 0) {
 #pragma unroll
@@ -247,317 +233,10 @@ __global__ void __launch_bounds__(128) k_fattn_combine_hd(const float * __restri
     }
 }
 
-// ------------------------------------------------------------------------------------------------ 33 tokens and more: the matrix cores at a padded head size
-typedef _Float16 hd_half8 __attribute__((ext_vector_type(8)));
-typedef _Float16 hd_half4 __attribute__((ext_vector_type(4)));
-typedef float hd_float16 __attribute__((ext_vector_type(16)));
-typedef uint32_t hd_u32x4 __attribute__((ext_vector_type(4)));
-
-struct fam_hd_geom {
-    int D, n_q, n_head, n_kv_head, n_kv, has_mask, n_splits;
-    float scale;
-};
-
-// k_fattn_mma's walk (fattn_mma.hip has the layout's reasons: S^T = K.Q^T with the query in the accumulator's column, V transposed while staged, tile states, the next
-// tile's loads in flight during the two GEMMs) at DP columns of which the first geo.D are real.
-// The 64-query workgroup at 128 columns holds 64 staging registers per thread and needs ~275: at two waves per SIMD (256 registers) it spills 17 of them, as
-// k_fattn_mma<128, 2> does; this form is told one wave per SIMD instead (two such workgroups per CU, not four) and keeps everything in registers.
-template <int DP, int NW>
-__global__ void __launch_bounds__(NW * 64, (DP == 128 && NW == 2) ? 1 : 2) k_fattn_mma_hd(const tdesc q, const tdesc k, const tdesc v, const tdesc mask, const tdesc dst, const fam_hd_geom geo, float * __restrict__ ws,
-                                                          const uint8_t * __restrict__ vis) {
-    static_assert(DP == 96 || DP == 128, "padded head sizes");
-    constexpr int TKV = 64;              // cells per tile
-    constexpr int KS = (DP + 8) * 2;     // K tile row stride (bytes): an odd multiple of 16 at both padded sizes (13, 17)
-    constexpr int VS = (TKV + 4) * 2;    // V^T tile row stride (bytes)
-    constexpr int NS = DP / 16;          // k-steps over the padded head dimension
-    constexpr int ND = DP / 32;          // output d-tiles
-    static_assert((KS / 16) % 2 == 1, "conflict-free ds_read_b128");
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    char * Kt = smem;                    // [TKV][DP + 8] f16, columns D .. DP - 1 zero
-    char * Vt = smem + TKV * KS;         // [DP][TKV + 4] f16 (transposed, swizzled), rows D .. DP - 1 zero
-
-    const int D = geo.D, nch = D >> 3;   // real 16-byte chunks of a K / V row
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int fr = lane & 31, kg = lane >> 5;
-    const int h = blockIdx.y, bat = blockIdx.z / geo.n_splits, split = blockIdx.z % geo.n_splits;
-    const int tiles = (geo.n_kv + TKV - 1) / TKV, tps = (tiles + geo.n_splits - 1) / geo.n_splits;
-    const int kv_begin = split * tps * TKV, kv_end = min(geo.n_kv, kv_begin + tps * TKV);
-    const int kvh = h / (geo.n_head / geo.n_kv_head);
-    const int qi = blockIdx.x * (NW * 32) + wave * 32 + fr;  // this lane's query token
-    const int qrow = min(qi, geo.n_q - 1);
-    const int64_t kb = bat / (q.ne[3] / k.ne[3]), vb = bat / (q.ne[3] / v.ne[3]);
-
-    // Q^T fragments: step s holds head dims 16s + 8kg .. + 7 of this lane's query — zeros where those are padding (72 / 88: the kg = 1 half of the last real step)
-    hd_half8 qf[NS];
-    {
-        const float * qp = (const float *) (q.data + (int64_t) qrow * q.nb[1] + (int64_t) h * q.nb[2] + (int64_t) bat * q.nb[3]);
-#pragma unroll
-        for (int s = 0; s < NS; ++s) {
-            float4 a = make_float4(0.0f, 0.0f, 0.0f, 0.0f), b = a;
-            if (2 * s + kg < nch) {
-                a = *(const float4 *) (qp + 16 * s + 8 * kg);
-                b = *(const float4 *) (qp + 16 * s + 8 * kg + 4);
-            }
-            qf[s] = (hd_half8){(_Float16) a.x, (_Float16) a.y, (_Float16) a.z, (_Float16) a.w, (_Float16) b.x, (_Float16) b.y, (_Float16) b.z, (_Float16) b.w};
-        }
-    }
-    const uint16_t * mrow = geo.has_mask ? (const uint16_t *) (mask.data + (int64_t) qrow * mask.nb[1] + (int64_t) (bat % mask.ne[3]) * mask.nb[3]) : nullptr;
-    const char * kbase = k.data + (int64_t) kvh * k.nb[2] + kb * k.nb[3];
-    const char * vbase = v.data + (int64_t) kvh * v.nb[2] + vb * v.nb[3];
-
-    constexpr float LOG2E = 1.4426950408889634f;
-    const float sc2 = geo.scale * LOG2E;
-    hd_float16 O[ND];
-#pragma unroll
-    for (int dt = 0; dt < ND; ++dt)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) O[dt][r] = 0.0f;
-    const hd_float16 zero = O[0];
-    float m = -INFINITY, l = 0.0f;
-
-    // staging roles.  K: thread -> cell and its CH chunks of the PADDED row (a padding chunk is stored as zeros).  V: thread -> blocks of 4 cells x 8 dims over the
-    // REAL chunks only; which block a thread takes does not change from tile to tile, so the division by the run-time chunk count is done once.
-    constexpr int T = NW * 64;
-    const int srow = tid / NW, spart = tid % NW;
-    constexpr int CH = DP / (8 * NW);
-    constexpr int VB = (16 * (DP / 8) + T - 1) / T;
-    const int nblk = 16 * nch;
-    int vblk[VB];  // (group of 4 cells) << 4 | chunk of the row, -1: this thread has no j-th block
-#pragma unroll
-    for (int j = 0; j < VB; ++j) {
-        const int b = tid + j * T;
-        vblk[j] = b < nblk ? ((b / nch) << 4) | (b % nch) : -1;
-    }
-    // the pad rows of V^T: nobody stages them and their output rows are never stored; zero, so that what the matrix cores read is defined
-    for (int i = tid; i < (DP - D) * (VS / 8); i += T) *(uint2 *) (Vt + D * VS + i * 8) = make_uint2(0u, 0u);
-
-    const int n_qt = (geo.n_q + 31) / 32;
-    const int kt_begin = kv_begin / TKV, kt_end = (kv_end + TKV - 1) / TKV;
-    uint8_t * const vt = (uint8_t *) (smem + TKV * KS + DP * VS);  // this split's tile states, the NW query tiles packed into a byte
-    if (vis) {
-        const uint8_t * visrow = vis + (int64_t) (blockIdx.x * NW) * tiles;
-        for (int i = kt_begin + tid; i < kt_end; i += T) {
-            uint32_t b = 0;
-#pragma unroll
-            for (int w = 0; w < NW; ++w)
-                if ((int) blockIdx.x * NW + w < n_qt) b |= (uint32_t) (visrow[(int64_t) w * tiles + i] & 3) << (2 * w);
-            vt[i - kt_begin] = (uint8_t) b;
-        }
-        __syncthreads();
-    }
-    auto next_tile = [&](int kt) __attribute__((always_inline)) {
-        if (vis)
-            while (kt < kt_end && __builtin_amdgcn_readfirstlane((int) vt[kt - kt_begin]) == 0) ++kt;
-        return kt;
-    };
-    hd_u32x4 kr[CH];
-    uint4 vr[VB][4];
-    auto load_tile = [&](const int kt) __attribute__((always_inline)) {
-        const int c0 = kt * TKV;
-        {
-            const int pos = min(c0 + srow, geo.n_kv - 1);
-            const hd_u32x4 * kp = (const hd_u32x4 *) (kbase + (int64_t) pos * k.nb[1]) + spart * CH;
-#pragma unroll
-            for (int i = 0; i < CH; ++i) {
-                kr[i] = (hd_u32x4){0u, 0u, 0u, 0u};
-                if (spart * CH + i < nch) kr[i] = kp[i];
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < VB; ++j) {
-            if (vblk[j] < 0) continue;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int pos = min(c0 + 4 * (vblk[j] >> 4) + r, geo.n_kv - 1);
-                vr[j][r] = *((const uint4 *) (vbase + (int64_t) pos * v.nb[1]) + (vblk[j] & 15));
-            }
-        }
-    };
-    auto store_tile = [&]() __attribute__((always_inline)) {
-#pragma unroll
-        for (int i = 0; i < CH; ++i) *(hd_u32x4 *) (Kt + srow * KS + (spart * CH + i) * 16) = kr[i];
-#pragma unroll
-        for (int j = 0; j < VB; ++j) {
-            if (vblk[j] < 0) continue;
-            const int kvq = vblk[j] >> 4, dch = vblk[j] & 15;
-            const uint32_t r0[4] = {vr[j][0].x, vr[j][0].y, vr[j][0].z, vr[j][0].w}, r1[4] = {vr[j][1].x, vr[j][1].y, vr[j][1].z, vr[j][1].w};
-            const uint32_t r2[4] = {vr[j][2].x, vr[j][2].y, vr[j][2].z, vr[j][2].w}, r3[4] = {vr[j][3].x, vr[j][3].y, vr[j][3].z, vr[j][3].w};
-            const int kvs = 8 * (kvq ^ (2 * (dch >> 2)));  // (groups of 4 cells XOR-swizzled by the row's 32-dim tile, as k_fattn_mma)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {  // dword e of a row holds head dims 2e, 2e + 1
-                uint2 lo, hi;
-                lo.x = __builtin_amdgcn_perm(r1[e], r0[e], 0x05040100u);
-                lo.y = __builtin_amdgcn_perm(r3[e], r2[e], 0x05040100u);
-                hi.x = __builtin_amdgcn_perm(r1[e], r0[e], 0x07060302u);
-                hi.y = __builtin_amdgcn_perm(r3[e], r2[e], 0x07060302u);
-                *(uint2 *) (Vt + (8 * dch + 2 * e) * VS + kvs) = lo;
-                *(uint2 *) (Vt + (8 * dch + 2 * e + 1) * VS + kvs) = hi;
-            }
-        }
-    };
-
-    int kt = next_tile(kt_begin);
-    if (kt < kt_end) load_tile(kt);
-    while (kt < kt_end) {
-        const int c0 = kt * TKV;
-        const int mine = !vis ? 1 : (int) __builtin_amdgcn_readfirstlane((vt[kt - kt_begin] >> (2 * wave)) & 3);
-        const bool tail = c0 + TKV > geo.n_kv;
-        __syncthreads();  // nobody reads the previous tile any more (the first time: the pad rows of V^T are written)
-        store_tile();
-        // the mask words of this tile (only where it is neither hidden nor plainly visible), requested BEFORE the next tile's K / V: vmcnt retires in order
-        uint2 mw[2][4] = {};
-        const bool use_mask = geo.has_mask != 0 && mine == 1;  // (wave-uniform)
-        if (use_mask) {
-#pragma unroll
-            for (int t = 0; t < 2; ++t)
-#pragma unroll
-                for (int g4 = 0; g4 < 4; ++g4) mw[t][g4] = *(const uint2 *) (mrow + min(c0 + 32 * t + 8 * g4 + 4 * kg, geo.n_kv - 4));
-        }
-        const int kt_next = next_tile(kt + 1);
-        if (kt_next < kt_end) load_tile(kt_next);
-        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-        kt = kt_next;
-        if (mine == 0) continue;  // none of this wave's queries sees the tile (the barriers are at the loop top)
-
-        hd_float16 S[2];
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-            S[t] = zero;
-#pragma unroll
-            for (int s = 0; s < NS; ++s) {
-                const hd_half8 a = *(const hd_half8 *) (Kt + (32 * t + fr) * KS + (16 * s + 8 * kg) * 2);
-                S[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, qf[s], S[t], 0, 0, 0);
-            }
-        }
-        float mx = -INFINITY;
-        if (use_mask || tail) {
-#pragma unroll
-            for (int t = 0; t < 2; ++t) {
-#pragma unroll
-                for (int g4 = 0; g4 < 4; ++g4) {
-                    const int p0 = c0 + 32 * t + 8 * g4 + 4 * kg;
-                    float mv[4] = {0.f, 0.f, 0.f, 0.f};
-                    if (use_mask) {
-                        mv[0] = h2f((uint16_t) (mw[t][g4].x & 0xFFFF)); mv[1] = h2f((uint16_t) (mw[t][g4].x >> 16));
-                        mv[2] = h2f((uint16_t) (mw[t][g4].y & 0xFFFF)); mv[3] = h2f((uint16_t) (mw[t][g4].y >> 16));
-                    }
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        float sv = fmaf(S[t][4 * g4 + e], sc2, mv[e] * LOG2E);
-                        if (p0 + e >= geo.n_kv) sv = -INFINITY;
-                        S[t][4 * g4 + e] = sv;
-                        mx = fmaxf(mx, sv);
-                    }
-                }
-            }
-        } else {
-#pragma unroll
-            for (int t = 0; t < 2; ++t)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const float sv = S[t][r] * sc2;
-                    S[t][r] = sv;
-                    mx = fmaxf(mx, sv);
-                }
-        }
-        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-        const float m_new = fmaxf(m, mx);
-        if (__all(m_new == -INFINITY)) continue;
-        const float mref = m_new == -INFINITY ? 0.0f : m_new;
-        const float alpha = __builtin_amdgcn_exp2f(m - mref);
-        float rs = 0.0f;
-#pragma unroll
-        for (int t = 0; t < 2; ++t)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const float p = __builtin_amdgcn_exp2f(S[t][r] - mref);
-                S[t][r] = p;
-                rs += p;
-            }
-        rs += __shfl_xor(rs, 32, 64);
-        l = l * alpha + rs;
-        m = m_new;
-        if (!__all(alpha == 1.0f)) {
-#pragma unroll
-            for (int dt = 0; dt < ND; ++dt)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) O[dt][r] *= alpha;
-        }
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-#pragma unroll
-            for (int s2 = 0; s2 < 2; ++s2) {
-                hd_half8 pb;
-#pragma unroll
-                for (int u = 0; u < 8; ++u) pb[u] = (_Float16) S[t][8 * s2 + u];
-                const int kvg = 8 * t + 4 * s2 + kg;
-#pragma unroll
-                for (int dt = 0; dt < ND; ++dt) {
-                    const char * vrow = Vt + (32 * dt + fr) * VS;
-                    const hd_half4 a0 = *(const hd_half4 *) (vrow + 8 * (kvg ^ (2 * dt))), a1 = *(const hd_half4 *) (vrow + 8 * ((kvg + 2) ^ (2 * dt)));
-                    const hd_half8 a = (hd_half8){a0[0], a0[1], a0[2], a0[3], a1[0], a1[1], a1[2], a1[3]};
-                    O[dt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, pb, O[dt], 0, 0, 0);
-                }
-            }
-        }
-    }
-    if (qi >= geo.n_q) return;
-    if (geo.n_splits == 1) {
-        const float inv = 1.0f / l;
-        float * out = (float *) (dst.data + (int64_t) h * dst.nb[1] + (int64_t) qi * dst.nb[2] + (int64_t) bat * dst.nb[3]);
-#pragma unroll
-        for (int dt = 0; dt < ND; ++dt)
-#pragma unroll
-            for (int g4 = 0; g4 < 4; ++g4) {
-                const int d0 = 32 * dt + 8 * g4 + 4 * kg;
-                if (d0 < D) *(float4 *) (out + d0) = make_float4(O[dt][4 * g4] * inv, O[dt][4 * g4 + 1] * inv, O[dt][4 * g4 + 2] * inv, O[dt][4 * g4 + 3] * inv);
-            }
-    } else {  // partial record (O relative to m, m, l) at the real stride
-        float * rec = ws + ((((int64_t) bat * geo.n_q + qi) * geo.n_head + h) * geo.n_splits + split) * (D + 2);
-#pragma unroll
-        for (int dt = 0; dt < ND; ++dt)
-#pragma unroll
-            for (int g4 = 0; g4 < 4; ++g4) {
-                const int d0 = 32 * dt + 8 * g4 + 4 * kg;
-                if (d0 < D) {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) rec[d0 + e] = O[dt][4 * g4 + e];
-                }
-            }
-        if (kg == 0) {
-            rec[D] = m * (1.0f / LOG2E);  // the combine pass works in the natural-log domain
-            rec[D + 1] = l;
-        }
-    }
-}
-
 // ------------------------------------------------------------------------------------------------ launchers
 void launch_fattn_combine_hd(hipStream_t s, int D, const float * ws, const float * sinks, const tdesc & dst, int n_q, int n_head, int n_batch, int n_splits) {
     if (!fattn_hd_size(D) || n_splits < 1 || n_splits > 64) { MI_ERR("launch_fattn_combine_hd: head_dim %d with %d splits is not served", D, n_splits); abort(); }
     hipLaunchKernelGGL(k_fattn_combine_hd, dim3((unsigned) n_head, (unsigned) n_q, (unsigned) n_batch), dim3(128), 0, s, ws, sinks, dst, D, n_q, n_head, n_splits);
-}
-
-void launch_fattn_mma_hd(hipStream_t s, const dim3 grid, int nw, size_t vt_bytes, const tdesc & q, const tdesc & k, const tdesc & v, const tdesc & mk, const tdesc & dst, bool has_mask, float scale,
-                         int n_splits, float * ws, const uint8_t * tile_vis) {
-    fam_hd_geom geo;
-    geo.D = (int) k.ne[0];
-    geo.n_q = (int) q.ne[1];
-    geo.n_head = (int) q.ne[2];
-    geo.n_kv_head = (int) k.ne[2];
-    geo.n_kv = (int) k.ne[1];
-    geo.has_mask = has_mask ? 1 : 0;
-    geo.n_splits = n_splits;
-    geo.scale = scale;
-    if (!fattn_hd_size(geo.D) || (nw != 2 && nw != 4)) { MI_ERR("launch_fattn_mma_hd: head_dim %d on %d waves is not served", geo.D, nw); abort(); }
-    const int DP = geo.D <= 96 ? 96 : 128;
-    const size_t lds = (size_t) 64 * (DP + 8) * 2 + (size_t) DP * (64 + 4) * 2 + vt_bytes;  // (at most 13 312 + 13 056 / 17 408 + 17 408 bytes of tiles + 16 384 states: below the 64 KB default)
-    if (DP == 96) {
-        if (nw == 4) hipLaunchKernelGGL((k_fattn_mma_hd<96, 4>), grid, dim3(256), lds, s, q, k, v, mk, dst, geo, ws, tile_vis);
-        else hipLaunchKernelGGL((k_fattn_mma_hd<96, 2>), grid, dim3(128), lds, s, q, k, v, mk, dst, geo, ws, tile_vis);
-    } else {
-        if (nw == 4) hipLaunchKernelGGL((k_fattn_mma_hd<128, 4>), grid, dim3(256), lds, s, q, k, v, mk, dst, geo, ws, tile_vis);
-        else hipLaunchKernelGGL((k_fattn_mma_hd<128, 2>), grid, dim3(128), lds, s, q, k, v, mk, dst, geo, ws, tile_vis);
-    }
 }
 
 // 1 .. 32 tokens, and every batch the matrix cores do not take (soft-capping, ALiBi, sinks, n_kv % 4 != 0): the split kernel and, behind two splits or more, the combine pass

@@ -31,23 +31,34 @@ struct fam_geom {
     int n_q, n_head, n_kv_head, n_kv, has_mask, n_splits;
     float scale;    // (soft-capped forms: scale / softcap)
     float softcap;  // head size 256 only (fattn_mma_d256)
+    int D;          // the real head size (read by the PAD forms only)
 };
 
 // NW waves of 32 queries each share one staged K/V tile (NW = 4: 128 queries per workgroup, half the staging work per query)
 // (D = 256 — Gemma — is specialised below, k_fattn_mma<256, NW, CAP>: a walk of its own on one wave per SIMD.  CAP, soft-capped scores, exists at that head size only)
-template <int D, int NW, bool CAP = false>
-__global__ void __launch_bounds__(NW * 64, 2) k_fattn_mma(const tdesc q, const tdesc k, const tdesc v, const tdesc mask, const tdesc dst, const fam_geom geo, float * __restrict__ ws,
-                                                       const uint8_t * __restrict__ vis) {
-    static_assert(!CAP && (D == 64 || D == 128), "head size 256 and soft-capping: the specialisations below");
+// PAD (head sizes 72 / 80 / 88 / 112, an f16 cache): the same walk at D = 96 / 128 COLUMNS of which the first geo.D (a run-time multiple of 8) are real.  The pad
+// columns of the staged K tile and the pad entries of the query fragments are WRITTEN as zeros and never loaded — the bytes behind a head's row belong to the next
+// head, the next cell or nobody, and 0 x NaN is NaN — so every padded product adds an exact zero; V is staged for the real geo.D / 8 chunks only (the pad rows of V^T
+// are zeroed once: their output rows are never stored); output and record stores skip the runs at d0 >= geo.D, records have the real stride geo.D + 2.  72 and 88
+// end in a half-live k-step (8 of its 16 dims).
+// The 64-query workgroup at 128 columns holds 64 staging registers per thread and needs ~275: at two waves per SIMD (256 registers) it spills 17 of them, as
+// k_fattn_mma<128, 2> does; the PAD form is told one wave per SIMD instead (two such workgroups per CU, not four) and keeps everything in registers.
+template <int D, int NW, bool CAP = false, bool PAD = false>
+__global__ void __launch_bounds__(NW * 64, (PAD && D == 128 && NW == 2) ? 1 : 2) k_fattn_mma(const tdesc q, const tdesc k, const tdesc v, const tdesc mask, const tdesc dst, const fam_geom geo,
+                                                                                          float * __restrict__ ws, const uint8_t * __restrict__ vis) {
+    static_assert(!CAP && (D == 64 || D == 128 || (PAD && D == 96)), "head size 256 and soft-capping: the specialisations below");
     constexpr int BKV = 64;
-    constexpr int KS = (D + 8) * 2;    // K tile row stride (bytes): odd multiple of 16 -> conflict-free ds_read_b128
+    constexpr int KS = (D + 8) * 2;    // K tile row stride (bytes): odd multiple of 16 (9, 13, 17) -> conflict-free ds_read_b128
     constexpr int VS = (BKV + 4) * 2;  // V^T tile row stride (bytes): 34 dwords -> conflict-free ds_read_b64 across 32 rows
     constexpr int NS = D / 16;         // MFMA k-steps over the head dimension
     constexpr int ND = D / 32;         // output d-tiles
+    static_assert((KS / 16) % 2 == 1, "conflict-free ds_read_b128");
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    char * Kt = smem;                  // [BKV][D+8] f16
-    char * Vt = smem + BKV * KS;       // [D][BKV+4] f16 (transposed)
+    char * Kt = smem;                  // [BKV][D+8] f16 (PAD: columns geo.D .. D - 1 zero)
+    char * Vt = smem + BKV * KS;       // [D][BKV+4] f16 (transposed; PAD: rows geo.D .. D - 1 zero)
 
+    const int DR = PAD ? geo.D : D;             // the real head size
+    [[maybe_unused]] const int nch = DR >> 3;  // its 16-byte chunks of a K / V row
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int fr = lane & 31, kg = lane >> 5;
     const int h = blockIdx.y, bat = blockIdx.z / geo.n_splits, split = blockIdx.z % geo.n_splits;
@@ -62,12 +73,19 @@ __global__ void __launch_bounds__(NW * 64, 2) k_fattn_mma(const tdesc q, const t
     const int64_t kb = bat / (q.ne[3] / k.ne[3]), vb = bat / (q.ne[3] / v.ne[3]);
 
     // Q^T fragments: step s needs head dims 16s + 8kg .. +7 of this lane's query (Q -> f16, as the CPU's q_to_vec_dot)
+    // — PAD: zeros where those are padding (72 / 88: the kg = 1 half of the last real step)
     half8 qf[NS];
     {
         const float * qp = (const float *) (q.data + (int64_t) qrow * q.nb[1] + (int64_t) h * q.nb[2] + (int64_t) bat * q.nb[3]);
 #pragma unroll
         for (int s = 0; s < NS; ++s) {
-            const float4 a = *(const float4 *) (qp + 16 * s + 8 * kg), b = *(const float4 *) (qp + 16 * s + 8 * kg + 4);
+            float4 a, b;
+            if constexpr (PAD) {
+                a = b = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+                if (2 * s + kg < nch) a = *(const float4 *) (qp + 16 * s + 8 * kg), b = *(const float4 *) (qp + 16 * s + 8 * kg + 4);
+            } else {
+                a = *(const float4 *) (qp + 16 * s + 8 * kg), b = *(const float4 *) (qp + 16 * s + 8 * kg + 4);
+            }
             qf[s] = (half8){(_Float16) a.x, (_Float16) a.y, (_Float16) a.z, (_Float16) a.w, (_Float16) b.x, (_Float16) b.y, (_Float16) b.z, (_Float16) b.w};
         }
     }
@@ -91,6 +109,18 @@ __global__ void __launch_bounds__(NW * 64, 2) k_fattn_mma(const tdesc q, const t
     const int srow = tid / NW, spart = tid % NW;
     constexpr int CH = D / (8 * NW);  // 16-byte chunks per thread per tile
     constexpr int NBLK = 16 * (D / 8), VB = (NBLK + T - 1) / T;
+    // PAD: K: a thread's chunks of the PADDED row (a padding chunk is stored as zeros).  V: blocks over the REAL chunks only; which block a thread takes does not
+    // change from tile to tile, so the division by the run-time chunk count is done once.
+    [[maybe_unused]] int vblk[PAD ? VB : 1];  // (group of 4 cells) << 4 | chunk of the row, -1: this thread has no j-th block
+    if constexpr (PAD) {
+#pragma unroll
+        for (int j = 0; j < VB; ++j) {
+            const int b = tid + j * T;
+            vblk[j] = b < 16 * nch ? ((b / nch) << 4) | (b % nch) : -1;
+        }
+        // the pad rows of V^T: nobody stages them and their output rows are never stored; zero, so that what the matrix cores read is defined
+        for (int i = tid; i < (D - DR) * (VS / 8); i += T) *(uint2 *) (Vt + DR * VS + i * 8) = make_uint2(0u, 0u);
+    }
 
     // vis (k_fattn_vis_scan, once per graph run — the mask is the same tensor in every layer): byte [q tile of 32][kv tile of 64]:
     // 0 = none of the 32 queries sees any of the 64 cells, 2 = every mask value of the tile is +0.0 (all visible, no bias: the kernel does
@@ -129,11 +159,25 @@ __global__ void __launch_bounds__(NW * 64, 2) k_fattn_mma(const tdesc q, const t
             const int pos = min(kv0 + srow, geo.n_kv - 1);
             const u32x4v * kp = (const u32x4v *) (kbase + (int64_t) pos * k.nb[1]) + spart * CH;
 #pragma unroll
-            for (int i = 0; i < CH; ++i) kr[i] = kp[i];
+            for (int i = 0; i < CH; ++i) {
+                if constexpr (PAD) {
+                    kr[i] = (u32x4v){0u, 0u, 0u, 0u};
+                    if (spart * CH + i < nch) kr[i] = kp[i];
+                } else {
+                    kr[i] = kp[i];
+                }
+            }
         }
 #pragma unroll
         for (int j = 0; j < VB; ++j) {
-            const int b = min(tid + j * T, NBLK - 1), kvq = b / (D / 8), dch = b % (D / 8);
+            int kvq, dch;
+            if constexpr (PAD) {
+                if (vblk[j] < 0) continue;
+                kvq = vblk[j] >> 4, dch = vblk[j] & 15;
+            } else {
+                const int b = min(tid + j * T, NBLK - 1);
+                kvq = b / (D / 8), dch = b % (D / 8);
+            }
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int pos = min(kv0 + 4 * kvq + r, geo.n_kv - 1);
@@ -146,9 +190,15 @@ __global__ void __launch_bounds__(NW * 64, 2) k_fattn_mma(const tdesc q, const t
         for (int i = 0; i < CH; ++i) *(u32x4v *) (Kt + srow * KS + (spart * CH + i) * 16) = kr[i];
 #pragma unroll
         for (int j = 0; j < VB; ++j) {
-            const int b = tid + j * T;
-            if (VB * T != NBLK && b >= NBLK) break;
-            const int kvq = b / (D / 8), dch = b % (D / 8);
+            int kvq, dch;
+            if constexpr (PAD) {
+                if (vblk[j] < 0) continue;
+                kvq = vblk[j] >> 4, dch = vblk[j] & 15;
+            } else {
+                const int b = tid + j * T;
+                if (VB * T != NBLK && b >= NBLK) break;
+                kvq = b / (D / 8), dch = b % (D / 8);
+            }
             const uint32_t r0[4] = {vr[j][0].x, vr[j][0].y, vr[j][0].z, vr[j][0].w}, r1[4] = {vr[j][1].x, vr[j][1].y, vr[j][1].z, vr[j][1].w};
             const uint32_t r2[4] = {vr[j][2].x, vr[j][2].y, vr[j][2].z, vr[j][2].w}, r3[4] = {vr[j][3].x, vr[j][3].y, vr[j][3].z, vr[j][3].w};
 #pragma unroll
@@ -173,7 +223,7 @@ __global__ void __launch_bounds__(NW * 64, 2) k_fattn_mma(const tdesc q, const t
         const int kv0 = kt * BKV;
         const int mine = !vis ? 1 : (int) __builtin_amdgcn_readfirstlane((vt[kt - kt_begin] >> (2 * wave)) & 3);
         const bool tail = kv0 + BKV > geo.n_kv;
-        __syncthreads();  // nobody reads the previous tile any more
+        __syncthreads();  // nobody reads the previous tile any more (PAD, the first time: the pad rows of V^T are written)
         store_tile();
         // the mask words of this tile (only where the tile is neither hidden nor plainly visible), requested BEFORE the next tile's K / V:
         // vmcnt retires in order, so waiting for them later leaves the younger K / V requests in flight
@@ -287,21 +337,23 @@ __global__ void __launch_bounds__(NW * 64, 2) k_fattn_mma(const tdesc q, const t
 #pragma unroll
                 for (int g4 = 0; g4 < 4; ++g4) {
                     const int d0 = 32 * dt + 8 * g4 + 4 * kg;
+                    if (PAD && d0 >= DR) continue;  // (a run of four is all real or all padding)
                     *(float4 *) (out + d0) = make_float4(O[dt][4 * g4] * inv, O[dt][4 * g4 + 1] * inv, O[dt][4 * g4 + 2] * inv, O[dt][4 * g4 + 3] * inv);
                 }
-        } else {  // partial record (O relative to m, m, l) in the layout k_fattn_combine reads
-            float * rec = ws + ((((int64_t) bat * geo.n_q + qi) * geo.n_head + h) * geo.n_splits + split) * (D + 2);
+        } else {  // partial record (O relative to m, m, l) in the layout k_fattn_combine reads: the real head size, stride DR + 2
+            float * rec = ws + ((((int64_t) bat * geo.n_q + qi) * geo.n_head + h) * geo.n_splits + split) * (DR + 2);
 #pragma unroll
             for (int dt = 0; dt < ND; ++dt)
 #pragma unroll
                 for (int g4 = 0; g4 < 4; ++g4) {
                     const int d0 = 32 * dt + 8 * g4 + 4 * kg;
+                    if (PAD && d0 >= DR) continue;
 #pragma unroll
                     for (int e = 0; e < 4; ++e) rec[d0 + e] = O[dt][4 * g4 + e];
                 }
             if (kg == 0) {
-                rec[D] = m * (1.0f / LOG2E);  // the combine pass works in the natural-log domain
-                rec[D + 1] = l;
+                rec[DR] = m * (1.0f / LOG2E);  // the combine pass works in the natural-log domain
+                rec[DR + 1] = l;
             }
         }
     }
@@ -925,11 +977,20 @@ static void launch_mma_d256(hipStream_t s, const dim3 grid, const size_t vt_byte
     (void) ensure_dyn_lds((const void *) k_fattn_mma<256, NW, CAP>, tiles_lds + 16384, lds_raised);  // (at most 16 384 tile states: below; on failure the launch fails and graph_compute reports it)
     hipLaunchKernelGGL((k_fattn_mma<256, NW, CAP>), grid, dim3(NW * 64), tiles_lds + vt_bytes, s, q, k, v, mk, dst, geo, ws, tile_vis);
 }
+// D columns (PAD: of which geo.D are real): at most 17 408 + 17 408 bytes of tiles + 16 384 states, below the 64 KB default
+template <int D, bool PAD>
+static void launch_mma(hipStream_t s, const dim3 grid, const int nw, const size_t vt_bytes, const tdesc & q, const tdesc & k, const tdesc & v, const tdesc & mk, const tdesc & dst, const fam_geom & geo,
+                       float * ws, const uint8_t * tile_vis) {
+    const size_t lds = 64 * (D + 8) * 2 + D * (64 + 4) * 2 + vt_bytes;
+    if (nw == 4) hipLaunchKernelGGL((k_fattn_mma<D, 4, false, PAD>), grid, dim3(256), lds, s, q, k, v, mk, dst, geo, ws, tile_vis);
+    else hipLaunchKernelGGL((k_fattn_mma<D, 2, false, PAD>), grid, dim3(128), lds, s, q, k, v, mk, dst, geo, ws, tile_vis);
+}
 bool launch_flash_attn_mma(hipStream_t s, const tdesc & q, const tdesc & k, const tdesc & v, const tdesc * mask, const float * sinks, const tdesc & dst,
                            const fattn_params & p, void * workspace) {
     const int D = (int) k.ne[0];
     if (!flash_attn_mma_applies(q, k, mask, sinks, dst, p)) return false;
     fam_geom geo;
+    geo.D = D;
     geo.n_q = (int) q.ne[1];
     geo.n_head = (int) q.ne[2];
     geo.n_kv_head = (int) k.ne[2];
@@ -949,18 +1010,15 @@ bool launch_flash_attn_mma(hipStream_t s, const tdesc & q, const tdesc & k, cons
     g_fa_form = fa_form_code(FA_FORM_K_MMA, tile_vis ? 1 : 0, nw, FA_FORM_KV_F16, D, FA_FORM_TAIL_NONE);  // (the combine pass adds which kernel merges)
     if (fattn_hd_size(D)) {  // the padded forms: 96 columns for 72 / 80 / 88, 128 for 112
         g_fa_form |= fa_form_hd(D);
-        launch_fattn_mma_hd(s, grid, nw, vt_bytes, q, k, v, mk, dst, mask != nullptr, geo.scale, geo.n_splits, ws, tile_vis);
+        if (D <= 96) launch_mma<96, true>(s, grid, nw, vt_bytes, q, k, v, mk, dst, geo, ws, tile_vis);
+        else launch_mma<128, true>(s, grid, nw, vt_bytes, q, k, v, mk, dst, geo, ws, tile_vis);
     } else if (D == 256) {
         if (nw == 4) { if (cap) launch_mma_d256<4, true>(s, grid, vt_bytes, q, k, v, mk, dst, geo, ws, tile_vis); else launch_mma_d256<4, false>(s, grid, vt_bytes, q, k, v, mk, dst, geo, ws, tile_vis); }
         else { if (cap) launch_mma_d256<2, true>(s, grid, vt_bytes, q, k, v, mk, dst, geo, ws, tile_vis); else launch_mma_d256<2, false>(s, grid, vt_bytes, q, k, v, mk, dst, geo, ws, tile_vis); }
     } else if (D == 128) {
-        const size_t lds = 64 * (128 + 8) * 2 + 128 * (64 + 4) * 2 + vt_bytes;
-        if (nw == 4) hipLaunchKernelGGL((k_fattn_mma<128, 4>), grid, dim3(256), lds, s, q, k, v, mk, dst, geo, ws, tile_vis);
-        else hipLaunchKernelGGL((k_fattn_mma<128, 2>), grid, dim3(128), lds, s, q, k, v, mk, dst, geo, ws, tile_vis);
+        launch_mma<128, false>(s, grid, nw, vt_bytes, q, k, v, mk, dst, geo, ws, tile_vis);
     } else {
-        const size_t lds = 64 * (64 + 8) * 2 + 64 * (64 + 4) * 2 + vt_bytes;
-        if (nw == 4) hipLaunchKernelGGL((k_fattn_mma<64, 4>), grid, dim3(256), lds, s, q, k, v, mk, dst, geo, ws, tile_vis);
-        else hipLaunchKernelGGL((k_fattn_mma<64, 2>), grid, dim3(128), lds, s, q, k, v, mk, dst, geo, ws, tile_vis);
+        launch_mma<64, false>(s, grid, nw, vt_bytes, q, k, v, mk, dst, geo, ws, tile_vis);
     }
     if (geo.n_splits > 1) launch_flash_attn_combine(s, (int) k.ne[0], ws, sinks, dst, (int) q.ne[1], (int) q.ne[2], (int) q.ne[3], geo.n_splits, p.q8_out);
     return true;

@@ -423,14 +423,12 @@ static inline int fa_form_code(int kernel, int mode, int waves, int kv, int D, i
     return kernel | (mode << 4) | (waves << 6) | (kv << 10) | ((D == 128 ? 1 : 0) << 12) | (tail << 13);
 }
 extern thread_local int g_fa_form;  // (fattn.hip)
-// ---- head sizes 72 / 80 / 88 / 112 (fattn_hd.hip): a row on 16 lanes of which D / 8 are live; the matrix cores at the padded size 96 / 128.  f16 K / V only.
+// ---- head sizes 72 / 80 / 88 / 112 (fattn_hd.hip): a row on 16 lanes of which D / 8 are live; the matrix cores at the padded size 96 / 128 (fattn_mma.hip: PAD).  f16 K / V only.
 static inline bool fattn_hd_size(int64_t D) { return D == 72 || D == 80 || D == 88 || D == 112; }
 // the head-size field a launcher ORs onto the head-size-64 code of its form (fa_form_tail leaves it alone: it rewrites bits 13..15)
 static inline int fa_form_hd(int64_t D) { return (D == 72 ? FA_FORM_HD_72 : D == 80 ? FA_FORM_HD_80 : D == 88 ? FA_FORM_HD_88 : D == 112 ? FA_FORM_HD_112 : 0) << FA_FORM_HD_SHIFT; }
 void launch_flash_attn_hd(hipStream_t s, const tdesc & q, const tdesc & k, const tdesc & v, const tdesc * mask, const float * sinks, const tdesc & dst, const fattn_params & p, void * workspace);
 void launch_fattn_combine_hd(hipStream_t s, int D, const float * ws, const float * sinks, const tdesc & dst, int n_q, int n_head, int n_batch, int n_splits);
-void launch_fattn_mma_hd(hipStream_t s, const dim3 grid, int nw, size_t vt_bytes, const tdesc & q, const tdesc & k, const tdesc & v, const tdesc & mk, const tdesc & dst, bool has_mask, float scale,
-                         int n_splits, float * ws, const uint8_t * tile_vis);
 
 // ---- the decode copy (repack.hip): rows [r0, r0 + n_rows) of a K-quant [K, N] matrix from the block layout at `src` into the plane layout at `dst` (same row stride)
 bool repack_supported(int type, int64_t K, int64_t nb1);

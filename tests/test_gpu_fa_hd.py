@@ -85,6 +85,73 @@ def test_fa_cells_hd(backend, H, plog, spec):
     assert not bad, f"{len(bad)} failures:\n" + "\n".join(bad[:12])
 
 
+# ------------------------------------------------------------------------------------------ one walk: the padded form against the full form
+def _node(H, D, NH, NKV, q, K, V, mask, scale):
+    """-> build(g): FLASH_ATTN_EXT over q [1, NH, nq, D] f32, K / V [nkv, NKV, D] f16 and an f16 mask (or None) with an EXPLICIT scale."""
+    nq, nkv = q.shape[2], K.shape[0]
+
+    def build(g):
+        tq = g.new(L.F32, [D, nq, NH, 1], q)
+        k = H.ggml_view_3d(g.ctx, g.new(L.F16, [NKV * D, nkv], K), D, nkv, NKV, 2 * NKV * D, 2 * D, 0)
+        v = H.ggml_view_3d(g.ctx, g.new(L.F16, [NKV * D, nkv], V), D, nkv, NKV, 2 * NKV * D, 2 * D, 0)
+        m = g.new(L.F16, [nkv, mask.shape[0]], mask) if mask is not None else None
+        r = H.ggml_flash_attn_ext(g.ctx, tq, k, v, m, scale, 0.0, 0.0)
+        H.ggml_flash_attn_ext_set_prec(r, 10)
+        return r
+
+    return build
+
+
+@pytest.mark.parametrize("nq,nkv,NH,NKV,masked", [(33, 68, 4, 2, True), (264, 132, 2, 1, False)], ids=["nw2_causal_at_end", "nw4_nomask"])
+def test_padded_form_equals_full_form_on_zero_padded_operands(backend, H, plog, nq, nkv, NH, NKV, masked):
+    """Head size 112 runs k_fattn_mma's PAD form at 128 columns; a head-size-128 node whose Q, K and V are the 112-wide ones with columns 112 .. 127 zero runs the
+    full form.  Same mask, the same explicit scale 1 / sqrt(112), one split (no combine pass: the two sizes merge records with different kernels).  The pad products
+    add exact zeros in the same matrix-core order, so the first 112 output columns are EQUAL as float values (-0 == +0); the pad columns of the 128 node are
+    compared with the float64 twin only (exact zeros there).  The masked shape (33 tokens at the end of 68 cells, two query tiles x two cell tiles) walks a diagonal
+    tile, a plainly visible one (the last token over cells 0 .. 63, no mask read) and the ragged four-cell tail under both query tiles; a causal mask at the cache's end
+    hides no tile at this shape."""
+    D, DP = 112, 128
+    scale = float(1.0 / np.sqrt(D))
+    rng = np.random.default_rng(112 * nq + nkv)
+    q = np.zeros((1, NH, nq, DP), np.float32)
+    K = np.zeros((nkv, NKV, DP), np.float16)
+    V = np.zeros((nkv, NKV, DP), np.float16)
+    q[..., :D] = rng.standard_normal((1, NH, nq, D)).astype(np.float32)
+    K[..., :D] = rng.standard_normal((nkv, NKV, D)).astype(np.float16)
+    V[..., :D] = rng.standard_normal((nkv, NKV, D)).astype(np.float16)
+    mask = None
+    if masked:  # causal at the cache's end: the last token sees every cell
+        mask = np.full(((nq + 63) // 64 * 64, nkv), -np.inf, np.float16)
+        for t in range(nq):
+            mask[t, : nkv - nq + t + 1] = 0
+    c = FR.fa_constants()
+    waves = c["nw_big"] if nq >= c["wg128_min_q"] else c["nw_small"]
+    mode = 1 if masked else 0
+    nodes = {
+        D: (_node(H, D, NH, NKV, np.ascontiguousarray(q[..., :D]), np.ascontiguousarray(K[..., :D]), np.ascontiguousarray(V[..., :D]), mask, scale), FH.form("MMA", mode, waves, D, "NONE")),
+        DP: (_node(H, DP, NH, NKV, q, K, V, mask, scale), FR.form("MMA", mode, waves, "F16", DP, "NONE")),
+    }
+    got = {}
+    backend.set_option("fa_splits", 1)
+    try:
+        for d, (build, form) in nodes.items():
+            assert F2.supported(backend, H, build), d
+            got[d] = np.asarray(T.run_case(build, backend)[0], np.float32).reshape(nq, NH, d)
+            ran = backend.stat("fa_form")
+            assert ran == form, f"head size {d}: expected form [{FH.form_name(form)}], ran [{FH.form_name(ran)}]"
+    finally:
+        backend.set_option("fa_splits", 0)
+    assert nodes[DP][1] & FH.hd_mask() == 0 and nodes[D][1] & FH.hd_mask() == FH.hd_field(D)
+    exact = F2.twin(q[0], K.astype(np.float64), V.astype(np.float64), mask, scale)  # [nq, NH, 128]
+    differ = np.argwhere(got[D] != got[DP][..., :D])
+    plog(f"fa_hd padded vs full nq={nq} nkv={nkv} waves={waves}: {len(differ)} of {got[D].size} values differ" + (f", first at {differ[0].tolist()}" if len(differ) else "")
+         + f"; vs twin: padded {T.nmse(got[D], exact[..., :D]):.3e}  full {T.nmse(got[DP], exact):.3e}")
+    assert not np.isnan(got[D]).any() and not np.isnan(got[DP]).any()
+    assert np.array_equal(got[D], got[DP][..., :D]), f"{len(differ)} values differ, columns {sorted(set(differ[:, 2].tolist()))[:16]}"
+    assert T.nmse(got[DP], exact) <= F2.TWIN_MMA
+    assert np.array_equal(got[DP][..., D:], exact[..., D:].astype(np.float32))
+
+
 # ------------------------------------------------------------------------------------------ hipGraph
 def _three_steps(backend, H, spec, x):
     """The node followed by eight SCALE nodes (a graph of nine nodes: the backend replays graphs of eight and more), computed three times on the same buffers."""
