@@ -278,6 +278,34 @@ static bool mm_id_ok(const ggml_tensor * op) {
     if (ids->ne[0] * ids->ne[1] > 65535 || a->ne[0] > INT32_MAX / 2 || a->ne[1] > INT32_MAX / 2 || a->ne[2] > INT32_MAX / 2) return false;
     return op->ne[0] == a->ne[1] && op->ne[1] == ids->ne[0] && op->ne[2] == ids->ne[1] && op->ne[3] == 1;
 }
+// the shapes and strides of a MUL_MAT_ID node as the launchers take them (the activations, the result and the bias are run_node's to fill in)
+static mmid_args mmid_operands(const ggml_tensor * op) {
+    const ggml_tensor * a = op->src[0];
+    const ggml_tensor * ids = op->src[2];
+    mmid_args m{};
+    m.W = (const uint8_t *) a->data;
+    m.w_nb1 = (int64_t) a->nb[1];
+    m.w_nb2 = (int64_t) a->nb[2];
+    m.type = (int) a->type;
+    m.K = (int) a->ne[0];
+    m.N = (int) a->ne[1];
+    m.n_expert = (int) a->ne[2];
+    m.ids = (const char *) ids->data;
+    m.ids_nb1 = (int64_t) ids->nb[1];
+    m.n_used = (int) ids->ne[0];
+    m.n_tokens = (int) ids->ne[1];
+    m.b_rows = (int) op->src[1]->ne[1];
+    return m;
+}
+// Which form serves a MUL_MAT_ID node — THE one place, asked by run_node and by plan_ws: the grouped matrix-core form (mmid_group.hip) for K-quant experts it can
+// tile (mmid_grouped_supported) from MI_MMID_GROUP_MIN_PAIRS pairs on; the mmid_group switch: 0 never, 1 routed, 2 wherever the operands allow, from 2 pairs on.
+// Everything else keeps the pair form (mmid.hip)
+static bool mmid_runs_grouped(const backend_ctx * c, const ggml_tensor * op) {
+    if (c->mmid_group == 0 || !mm_id_ok(op)) return false;
+    const mmid_args m = mmid_operands(op);
+    if ((int64_t) m.n_used * m.n_tokens < (c->mmid_group == 2 ? 2 : MI_MMID_GROUP_MIN_PAIRS)) return false;
+    return mmid_grouped_supported(m);
+}
 // ADD_ID (mmid.hip): a f32 [n, n_used, n_tokens] with contiguous rows at element-aligned strides; b f32 [n, n_expert] with contiguous rows; ids I32 [n_used, n_tokens],
 // possibly a strided view (mm_id_ok's conditions); dst f32 contiguous.  dst(:, s, t) = a(:, s, t) + b(:, ids(s, t)).  Shapes, types and strides only.
 static bool add_id_ok(const ggml_tensor * op) {
@@ -694,6 +722,8 @@ static ws_plan plan_ws(backend_ctx * c, const ggml_cgraph * g) {
         } else if (n->op == GGML_OP_MUL_MAT_ID && is_quant(n->src[0]->type)) {  // every distinct row of b, quantised once
             const ggml_tensor * b = n->src[1];
             p.act_bytes = std::max(p.act_bytes, quantized_act_bytes(act_kind(n->src[0]->type), b->ne[0], b->ne[1] * b->ne[2] * b->ne[3]));
+            // the grouped form's tile table and permutation: a captured graph never grows the scratch
+            if (mmid_runs_grouped(c, n)) p.aux_bytes = std::max(p.aux_bytes, mmid_group_scratch_bytes(n->src[2]->ne[0] * n->src[2]->ne[1], n->src[0]->ne[2]));
         } else if (mm_image) {
             const tdesc a16 = kv_image_desc(TD(n->src[0]), nullptr);
             p.aux_bytes = std::max(p.aux_bytes, ((mul_mat_f_workspace_bytes(a16, TD(n->src[1])) + 255) & ~(size_t) 255) + kv_image_bytes(a16));
@@ -2484,19 +2514,7 @@ static int run_node(exec_state & st, int i) {
                 MI_ERR("graph_compute: node %d '%s': MUL_MAT_ID operands the backend does not serve (supports_op answers false for them)", i, n->name);
                 return -1;
             }
-            mmid_args m{};
-            m.W = (const uint8_t *) a->data;
-            m.w_nb1 = (int64_t) a->nb[1];
-            m.w_nb2 = (int64_t) a->nb[2];
-            m.type = (int) a->type;
-            m.K = (int) a->ne[0];
-            m.N = (int) a->ne[1];
-            m.n_expert = (int) a->ne[2];
-            m.ids = (const char *) ids->data;
-            m.ids_nb1 = (int64_t) ids->nb[1];
-            m.n_used = (int) ids->ne[0];
-            m.n_tokens = (int) ids->ne[1];
-            m.b_rows = (int) b->ne[1];
+            mmid_args m = mmid_operands(n);
             // MUL_MAT_ID -> ADD_ID (gpt-oss's per-expert bias): the ADD_ID directly behind this node, this result's only reader, over the same ids tensor, rides in
             // the store.  The launch then writes the ADD_ID's block: not when that block is one a workgroup still reads (the bias, the ids, or b — the f16 / f32
             // expert kernels read b itself while other workgroups store).  The quantised kernels read b's blocks in the activation area, not b, so for them an
@@ -2520,10 +2538,18 @@ static int run_node(exec_state & st, int i) {
                 m.x_nb1 = (int64_t) b->nb[1];
                 m.x_nb2 = (int64_t) b->nb[2];
             }
-            // (bytes: the expert matrices the pairs stream, counted once per pair)
-            timed_scope ts(c, (std::string("mmid_") + type_tag(a->type)).c_str(), (double) (a->nb[2] * (size_t) (ids->ne[0] * ids->ne[1])));
-            launch_mmid(s, m);
-            c->st.kernel_launches++;
+            if (mmid_runs_grouped(c, n)) {
+                // (bytes: an expert matrix once per 32-column tile, the worst routing of this shape)
+                const int64_t pairs = (int64_t) m.n_used * m.n_tokens;
+                timed_scope ts(c, (std::string("mmid_grp_") + type_tag(a->type)).c_str(), (double) a->nb[2] * (double) mmid_group_max_tiles(pairs, m.n_expert));
+                if (!launch_mmid_grouped(s, m, c->ws ? (char *) c->ws + st.aux_off : nullptr, c->ws && c->ws_size > st.aux_off ? c->ws_size - st.aux_off : 0)) return -1;
+                c->st.kernel_launches += 2;  // the grouping kernel and the product
+            } else {
+                // (bytes: the expert matrices the pairs stream, counted once per pair)
+                timed_scope ts(c, (std::string("mmid_") + type_tag(a->type)).c_str(), (double) (a->nb[2] * (size_t) (ids->ne[0] * ids->ne[1])));
+                launch_mmid(s, m);
+                c->st.kernel_launches++;
+            }
             c->st.mmid_launches++;
             if (bias) {
                 c->st.fused_nodes += 1;

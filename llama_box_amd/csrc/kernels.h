@@ -119,6 +119,21 @@ struct mmid_args {
     int64_t bias_nb1;
 };
 void launch_mmid(hipStream_t s, const mmid_args & a);
+// The grouped form (mmid_group.hip): the pairs ordered by expert on the device (k_mmid_group), then every expert's pairs as the columns of the integer matrix-core
+// unit (k_mmid_grouped: two launches a node).  Q4_K / Q5_K / Q6_K experts of whole super-blocks and 32-row panels with packed rows (mmid_grouped_supported).
+//   MI_MMID_GROUP_MIN_PAIRS   routed (mmid_group 1): n_used * n_tokens from which a node takes the grouped form.  Never below 33: up to 32 pairs a result is promised
+//                             bit-equal to the backend's one-column MUL_MAT, which is k_mmid's arithmetic.  Measured on the MI355X, grouped form forced on against
+//                             the pair form, hipEvent-bracketed per node, medians of five windows (scripts/ubench/mmid_bench.py --group 0,2 --windows 5,
+//                             profiles/mmid_grouped_ubench.txt): Mixtral (2 of 8) wins from 16 pairs on, Qwen3 (8 of 128: one pair an expert at 128 pairs) still loses 7 %
+//                             at 128 pairs (up: 38.4 against 35.8 us) and wins at 256 (49.2 against 65.6 us); Q5_K / Q6_K win from 128 pairs on — 256 is the smallest
+//                             measured count from which no shape of any of the three formats is slower.
+//   MI_MMID_GROUP_MAX_EXPERT  experts the grouping kernel's LDS histogram holds (one more entry takes the ids outside the experts)
+#define MI_MMID_GROUP_MIN_PAIRS 256
+#define MI_MMID_GROUP_MAX_EXPERT 1024
+bool mmid_grouped_supported(const mmid_args & a);
+int64_t mmid_group_max_tiles(int64_t n_pairs, int64_t n_expert);     // 32-column tiles of the worst routing: floor(P / 32) + min(n_expert + 1, P)
+size_t mmid_group_scratch_bytes(int64_t n_pairs, int64_t n_expert);  // header + tile table + permutation (plan_ws: aux_bytes; the launcher refuses less)
+bool launch_mmid_grouped(hipStream_t s, const mmid_args & a, void * scratch, size_t scratch_bytes);
 // ADD_ID on its own: dst(:, s, t) = a(:, s, t) + b(:, ids(s, t)); a f32 [n, n_used, n_tokens] with contiguous rows, b f32 [n, n_expert], ids I32 (token stride nb[1])
 void launch_add_id(hipStream_t s, const tdesc & a, const tdesc & b, const tdesc & ids, const tdesc & dst);
 
@@ -517,6 +532,7 @@ void tu_touch_tp_p2p(hipStream_t s);
 void tu_touch_kv_types(hipStream_t s);
 void tu_touch_repack(hipStream_t s);
 void tu_touch_mmid(hipStream_t s);
+void tu_touch_mmid_group(hipStream_t s);
 void tu_touch_mmb(hipStream_t s);
 void tu_touch_ssm(hipStream_t s);
 void tu_touch_rwkv(hipStream_t s);
@@ -528,6 +544,7 @@ inline void preload_kernel_files(hipStream_t s) {
     tu_touch_quantize(s);
     tu_touch_mmvq(s);
     tu_touch_mmid(s);
+    tu_touch_mmid_group(s);
     tu_touch_mmb(s);
     tu_touch_qkv(s);
     tu_touch_mmf(s);

@@ -1,7 +1,9 @@
 """Batch-1 MUL_MAT_ID launches (up / gate and down nodes of the Mixtral and Qwen3-30B-A3B expert shapes) next to the dense one-column mat-vec of a 2-D
 matrix of the same type and the same byte count (n_used * N rows).  Run it under `rocprofv3 --kernel-trace --stats -d DIR -o mmid -- python
 scripts/ubench/mmid_bench.py [type] [n_tokens]` and read the trace with `scripts/trace_by_grid.py DIR/.../mmid_kernel_trace.csv k_mm` (every configuration has a
-grid size of its own); with n_tokens > 1 (the larger-batch form: the same launch over more pairs) the dense yardstick is the batch mat-mul of that matrix
+grid size of its own); `--group 0,2` times the node under each value of the backend's mmid_group switch (0: the pair form, 2: the grouped matrix-core form forced on), `--windows 5` takes
+five windows per cell (median, lowest, highest);
+with n_tokens > 1 (the larger-batch form: the same launch over more pairs) the dense yardstick is the batch mat-mul of that matrix
 with n_tokens columns.  The script itself prints the hipEvent-bracketed class times of the backend's timing option as a cross-check."""
 import ctypes as C
 import os
@@ -38,11 +40,23 @@ def run(be, build, reps):
         g.free()
 
 
+def take(flag, default):
+    if flag not in sys.argv:
+        return default
+    i = sys.argv.index(flag)
+    v = sys.argv[i + 1]
+    del sys.argv[i:i + 2]
+    return v
+
+
 def main():
+    """mmid_bench.py [type] [n_tokens[,n_tokens..]] [--group G[,G..]] [--windows W]: every shape's weights are made once and serve all token counts and forms;
+    a cell is the median over W windows (default 1) of the mean of `reps` launches, printed with the windows' lowest and highest mean."""
+    groups = [None if g == "" else int(g) for g in take("--group", "").split(",")]
+    windows = int(take("--windows", "1"))
     tname = sys.argv[1] if len(sys.argv) > 1 else "q4_K"
     qtype = TYPES[tname]
-    n_tok = int(sys.argv[2]) if len(sys.argv) > 2 else 1
-    reps = 50 if n_tok == 1 else 10
+    toks = [int(t) for t in (sys.argv[2] if len(sys.argv) > 2 else "1").split(",")]
     be = L.Backend(0)
     be.set_option("graphs", 0)
     be.set_option("timing", 1)
@@ -51,29 +65,36 @@ def main():
     for name, (K, N, n_expert, n_used, per_slot) in SHAPES.items():
         row_bytes = K // L.TYPE_BLCK[qtype] * L.TYPE_SIZE[qtype]
         W = np.stack([T.rand_weight(qtype, K, N, rng) for _ in range(n_expert)])
-        ids = np.stack([rng.permutation(n_expert)[:n_used] for _ in range(n_tok)]).astype(np.int32)
-        b = rng.standard_normal((n_tok, n_used if per_slot else 1, K)).astype(np.float32)
-        full = np.zeros((n_tok, n_expert), dtype=np.int32)
-        full[:, :n_used] = ids
+        for n_tok in toks:
+            reps = 50 if n_tok == 1 else 10
+            ids = np.stack([rng.permutation(n_expert)[:n_used] for _ in range(n_tok)]).astype(np.int32)
+            b = rng.standard_normal((n_tok, n_used if per_slot else 1, K)).astype(np.float32)
+            full = np.zeros((n_tok, n_expert), dtype=np.int32)
+            full[:, :n_used] = ids
 
-        def moe(g):
-            as_t = g.new(qtype, [K, N, n_expert], W)
-            idt = H.ggml_view_2d(g.ctx, g.new(L.I32, [n_expert, n_tok], full), n_used, n_tok, n_expert * 4, 0)
-            return H.ggml_mul_mat_id(g.ctx, as_t, g.new(L.F32, [K, b.shape[1], n_tok], b), idt)
+            def moe(g):
+                as_t = g.new(qtype, [K, N, n_expert], W)
+                idt = H.ggml_view_2d(g.ctx, g.new(L.I32, [n_expert, n_tok], full), n_used, n_tok, n_expert * 4, 0)
+                return H.ggml_mul_mat_id(g.ctx, as_t, g.new(L.F32, [K, b.shape[1], n_tok], b), idt)
 
-        def dense(g):
-            w = g.new(qtype, [K, n_used * N], W[:n_used].reshape(n_used * N, -1))
-            return H.ggml_mul_mat(g.ctx, w, g.new(L.F32, [K, n_tok], np.ascontiguousarray(b[:, 0])))
+            def dense(g):
+                w = g.new(qtype, [K, n_used * N], W[:n_used].reshape(n_used * N, -1))
+                return H.ggml_mul_mat(g.ctx, w, g.new(L.F32, [K, n_tok], np.ascontiguousarray(b[:, 0])))
 
-        for kind, fn in (("mul_mat_id", moe), ("dense", dense)):
-            be.timing_report(reset=True)
-            run(be, fn, reps)
-            rep = be.timing_report(reset=True)
-            nbytes = n_used * N * row_bytes
-            for cls, (cnt, ms, _) in sorted(rep.items()):
-                if cnt and (cls.startswith("mmid") or cls.startswith("mmvq") or cls.startswith("mmq")):
-                    us = ms * 1e3 / cnt
-                    print(f"{tname} n_tokens={n_tok} {name:13s} {kind:10s} {cls:28s} n={cnt:3d} {us:8.2f} us/launch {nbytes / 1e6:7.1f} MB {nbytes / us / 1e6:7.3f} TB/s", flush=True)
+            for kind, fn, grp in [("mul_mat_id", moe, g) for g in groups] + [("dense", dense, None)]:
+                if grp is not None:
+                    be.set_option("mmid_group", grp)
+                per = {}
+                for _ in range(windows):
+                    be.timing_report(reset=True)
+                    run(be, fn, reps)
+                    for cls, (cnt, ms, _) in be.timing_report(reset=True).items():
+                        if cnt and (cls.startswith("mmid") or cls.startswith("mmvq") or cls.startswith("mmq")):
+                            per.setdefault(cls, []).append(ms * 1e3 / cnt)
+                nbytes = n_used * N * row_bytes
+                for cls, v in sorted(per.items()):
+                    us = float(np.median(v))
+                    print(f"{tname} n_tokens={n_tok} {name:13s} {kind:10s} group={grp} {cls:28s} windows={len(v)} {us:8.2f} us/launch (min {min(v):.2f} max {max(v):.2f}) {nbytes / 1e6:7.1f} MB {nbytes / us / 1e6:7.3f} TB/s", flush=True)
     be.close()
 
 
