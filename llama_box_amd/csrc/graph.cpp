@@ -90,8 +90,9 @@ static inline int mmq_min_cols_for(const backend_ctx * c, int wtype) {
     // The hand-over was set where the one-pass form ends and not compared with other thresholds.
     // IQ4_XS: the same hand-over, taken from Q2_K / Q3_K and not compared with other thresholds either.
     if (is_kq23_type(wtype) || is_iq4xs_type(wtype)) return 9;
-    // MXFP4: never — no matrix-core form reads the format (mmq_q80.hip's staging carries the block scale as f16, which an E8M0 scale does not fit), so batch_form
-    // answers MM_VEC for every M and plan_ws sizes no split-K area for it
+    // MXFP4: never — no matrix-core form of the dense MUL_MAT reads the format (mmq_q80.hip's staging carries the block scale as f16, which an E8M0 scale does not
+    // fit; the one that does, mmid_group_mxfp4.hip, serves MUL_MAT_ID, and no gpt-oss file has a dense MXFP4 matrix), so batch_form answers MM_VEC for every M and
+    // plan_ws sizes no split-K area for it
     if (is_mxfp4_type(wtype)) return INT32_MAX;
     if (c->opt.mmq_min_cols != 3) return c->opt.mmq_min_cols;
     return (wtype == GGML_TYPE_Q4_K || (wtype == GGML_TYPE_Q6_K && !c->mm_q5_major)) ? 2 : 3;
@@ -297,13 +298,14 @@ static mmid_args mmid_operands(const ggml_tensor * op) {
     m.b_rows = (int) op->src[1]->ne[1];
     return m;
 }
-// Which form serves a MUL_MAT_ID node — THE one place, asked by run_node and by plan_ws: the grouped matrix-core form (mmid_group.hip) for K-quant experts it can
-// tile (mmid_grouped_supported) from MI_MMID_GROUP_MIN_PAIRS pairs on; the mmid_group switch: 0 never, 1 routed, 2 wherever the operands allow, from 2 pairs on.
-// Everything else keeps the pair form (mmid.hip)
+// Which form serves a MUL_MAT_ID node — THE one place, asked by run_node and by plan_ws: the grouped matrix-core form (mmid_group.hip; MXFP4: mmid_group_mxfp4.hip)
+// for K-quant and MXFP4 experts it can tile (mmid_grouped_supported) from MI_MMID_GROUP_MIN_PAIRS / MI_MMID_GROUP_MXFP4_MIN_PAIRS pairs on; the mmid_group switch:
+// 0 never, 1 routed, 2 wherever the operands allow, from 2 pairs on.  Everything else keeps the pair form (mmid.hip)
 static bool mmid_runs_grouped(const backend_ctx * c, const ggml_tensor * op) {
     if (c->mmid_group == 0 || !mm_id_ok(op)) return false;
     const mmid_args m = mmid_operands(op);
-    if ((int64_t) m.n_used * m.n_tokens < (c->mmid_group == 2 ? 2 : MI_MMID_GROUP_MIN_PAIRS)) return false;
+    const int min_pairs = is_mxfp4_type(m.type) ? MI_MMID_GROUP_MXFP4_MIN_PAIRS : MI_MMID_GROUP_MIN_PAIRS;
+    if ((int64_t) m.n_used * m.n_tokens < (c->mmid_group == 2 ? 2 : min_pairs)) return false;
     return mmid_grouped_supported(m);
 }
 // ADD_ID (mmid.hip): a f32 [n, n_used, n_tokens] with contiguous rows at element-aligned strides; b f32 [n, n_expert] with contiguous rows; ids I32 [n_used, n_tokens],

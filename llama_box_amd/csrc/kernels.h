@@ -120,20 +120,47 @@ struct mmid_args {
 };
 void launch_mmid(hipStream_t s, const mmid_args & a);
 // The grouped form (mmid_group.hip): the pairs ordered by expert on the device (k_mmid_group), then every expert's pairs as the columns of the integer matrix-core
-// unit (k_mmid_grouped: two launches a node).  Q4_K / Q5_K / Q6_K experts of whole super-blocks and 32-row panels with packed rows (mmid_grouped_supported).
+// unit (k_mmid_grouped: two launches a node).  Q4_K / Q5_K / Q6_K experts of whole super-blocks and 32-row panels with packed rows, and MXFP4 experts of whole
+// 32-value blocks and 32-row panels with packed rows at any byte alignment (k_mmid_grouped_mxfp4, mmid_group_mxfp4.hip) (mmid_grouped_supported).
 //   MI_MMID_GROUP_MIN_PAIRS   routed (mmid_group 1): n_used * n_tokens from which a node takes the grouped form.  Never below 33: up to 32 pairs a result is promised
 //                             bit-equal to the backend's one-column MUL_MAT, which is k_mmid's arithmetic.  Measured on the MI355X, grouped form forced on against
 //                             the pair form, hipEvent-bracketed per node, medians of five windows (scripts/ubench/mmid_bench.py --group 0,2 --windows 5,
 //                             profiles/mmid_grouped_ubench.txt): Mixtral (2 of 8) wins from 16 pairs on, Qwen3 (8 of 128: one pair an expert at 128 pairs) still loses 7 %
 //                             at 128 pairs (up: 38.4 against 35.8 us) and wins at 256 (49.2 against 65.6 us); Q5_K / Q6_K win from 128 pairs on — 256 is the smallest
 //                             measured count from which no shape of any of the three formats is slower.
+//   MI_MMID_GROUP_MXFP4_MIN_PAIRS  the same hand-over for MXFP4 experts (mmid_group_mxfp4.hip).  Never below 128: an 80-pair MXFP4 node is held bit-equal to the mat-vec.
+//                             Measured the same way on the gpt-oss shapes (K = N = 2880, ADD_ID in the store; scripts/ubench/mmid_bench.py mxfp4 --group 0,2 --windows 5,
+//                             profiles/mmid_grouped_mxfp4_ubench.txt): 4 of 32 experts win from 128 pairs on (124 against 162 us), 4 of 128 experts — two pairs an
+//                             expert at 256 pairs — still lose 18 % at 256 pairs (425 against 361 us) and win at 512 (483 against 715 us): 512 is the smallest
+//                             measured count from which no measured shape is slower.
 //   MI_MMID_GROUP_MAX_EXPERT  experts the grouping kernel's LDS histogram holds (one more entry takes the ids outside the experts)
 #define MI_MMID_GROUP_MIN_PAIRS 256
+#define MI_MMID_GROUP_MXFP4_MIN_PAIRS 512
 #define MI_MMID_GROUP_MAX_EXPERT 1024
 bool mmid_grouped_supported(const mmid_args & a);
 int64_t mmid_group_max_tiles(int64_t n_pairs, int64_t n_expert);     // 32-column tiles of the worst routing: floor(P / 32) + min(n_expert + 1, P)
 size_t mmid_group_scratch_bytes(int64_t n_pairs, int64_t n_expert);  // header + tile table + permutation (plan_ws: aux_bytes; the launcher refuses less)
 bool launch_mmid_grouped(hipStream_t s, const mmid_args & a, void * scratch, size_t scratch_bytes);
+// A node's scratch as k_mmid_group leaves it and the product kernels of both files read it, 16-byte aligned:
+//   hdr    MI_MMID_GROUP_HDR_BYTES; hdr[0] = the number of tiles
+//   tiles  max_tiles records {x: expert, -1 for the pseudo-group of ids outside [0, n_expert); y: first index in perm; z: live columns 1 .. 32; w: 0}
+//   perm   the pair indices tok * n_used + slot ordered by group (n_pairs ints, rounded up to four)
+#define MI_MMID_GROUP_HDR_BYTES 64
+struct mmid_group_scratch {
+    int * hdr;
+    int4 * tiles;
+    int * perm;
+    int max_tiles;
+};
+inline mmid_group_scratch mmid_group_layout(void * scratch, int64_t n_pairs, int64_t n_expert) {
+    mmid_group_scratch g;
+    g.max_tiles = (int) mmid_group_max_tiles(n_pairs, n_expert);
+    g.hdr = (int *) scratch;
+    g.tiles = (int4 *) ((char *) scratch + MI_MMID_GROUP_HDR_BYTES);
+    g.perm = (int *) (g.tiles + g.max_tiles);
+    return g;
+}
+void launch_mmid_grouped_mxfp4(hipStream_t s, const mmid_args & a, const mmid_group_scratch & g);  // the product over MXFP4 experts (launch_mmid_grouped calls it)
 // ADD_ID on its own: dst(:, s, t) = a(:, s, t) + b(:, ids(s, t)); a f32 [n, n_used, n_tokens] with contiguous rows, b f32 [n, n_expert], ids I32 (token stride nb[1])
 void launch_add_id(hipStream_t s, const tdesc & a, const tdesc & b, const tdesc & ids, const tdesc & dst);
 
@@ -533,6 +560,7 @@ void tu_touch_kv_types(hipStream_t s);
 void tu_touch_repack(hipStream_t s);
 void tu_touch_mmid(hipStream_t s);
 void tu_touch_mmid_group(hipStream_t s);
+void tu_touch_mmid_group_mxfp4(hipStream_t s);
 void tu_touch_mmb(hipStream_t s);
 void tu_touch_ssm(hipStream_t s);
 void tu_touch_rwkv(hipStream_t s);
@@ -545,6 +573,7 @@ inline void preload_kernel_files(hipStream_t s) {
     tu_touch_mmvq(s);
     tu_touch_mmid(s);
     tu_touch_mmid_group(s);
+    tu_touch_mmid_group_mxfp4(s);
     tu_touch_mmb(s);
     tu_touch_qkv(s);
     tu_touch_mmf(s);

@@ -1,5 +1,6 @@
 // mmid_group.hip — MUL_MAT_ID for batches: the (slot, token) pairs grouped by expert ON THE DEVICE, and each group's pairs multiplied as the columns of
-// the integer matrix-core unit of mmq_unit.h (K-quant experts: Q4_K / Q5_K / Q6_K).
+// the integer matrix-core unit of mmq_unit.h (K-quant experts: Q4_K / Q5_K / Q6_K).  MXFP4 experts share the grouping kernel and the scratch layout; their
+// product kernel is mmid_group_mxfp4.hip's.
 //
 // mmid.hip serves a batch as n_used * n_tokens independent mat-vecs: every pair streams its whole expert matrix and does one column of v_dot4 arithmetic per
 // weight byte.  Here a weight byte read from memory meets up to 32 columns:
@@ -32,8 +33,8 @@
 
 namespace mi355x {
 
-// scratch of one node: [16 ints: n_tiles, ..][tile records, 16 bytes each][perm]
-constexpr size_t GR_HDR_BYTES = 64;
+// scratch of one node: [16 ints: n_tiles, ..][tile records, 16 bytes each][perm] (kernels.h: mmid_group_scratch)
+constexpr size_t GR_HDR_BYTES = MI_MMID_GROUP_HDR_BYTES;
 int64_t mmid_group_max_tiles(int64_t n_pairs, int64_t n_expert) { return n_pairs / 32 + std::min(n_expert + 1, n_pairs); }
 size_t mmid_group_scratch_bytes(int64_t n_pairs, int64_t n_expert) {
     return GR_HDR_BYTES + (size_t) mmid_group_max_tiles(n_pairs, n_expert) * sizeof(int4) + (((size_t) n_pairs + 3) & ~(size_t) 3) * sizeof(int32_t);
@@ -279,13 +280,17 @@ template <int QT> static bool launch_grouped_t(hipStream_t s, const mmid_args & 
 }
 
 // the operands the grouped form serves (graph.cpp's mmid_runs_grouped adds the pair threshold and the switch): K-quant experts of whole super-blocks and whole
-// 32-row panels, rows packed back to back; Q6_K: every row of every expert dword-aligned, so that the 0 / 2-byte shift of a super-block is the same in all of them
+// 32-row panels, rows packed back to back; Q6_K: every row of every expert dword-aligned, so that the 0 / 2-byte shift of a super-block is the same in all of them;
+// MXFP4 experts (mmid_group_mxfp4.hip) of whole 32-value blocks and whole 32-row panels, rows packed back to back at any byte alignment
 bool mmid_grouped_supported(const mmid_args & a) {
-    if (a.K < 256 || (a.K % 256) != 0 || a.N < 32 || (a.N % 32) != 0 || a.n_expert < 1 || a.n_expert > MI_MMID_GROUP_MAX_EXPERT) return false;
+    const bool mx = a.type == GGML_TYPE_MXFP4;
+    const int blk = mx ? 32 : 256;
+    if (a.K < blk || (a.K % blk) != 0 || a.N < 32 || (a.N % 32) != 0 || a.n_expert < 1 || a.n_expert > MI_MMID_GROUP_MAX_EXPERT) return false;
     if (a.n_used < 1 || a.n_tokens < 1 || (int64_t) a.n_used * a.n_tokens >= 65536 || (a.b_rows != 1 && a.b_rows != a.n_used)) return false;
-    const int64_t nblk = a.K / 256;
-    if ((int64_t) a.n_tokens * a.b_rows * nblk * (int64_t) sizeof(q8k_dev) >= INT32_MAX) return false;  // (the gather's 32-bit lane offsets into the activation area)
-    if (mmid_group_max_tiles((int64_t) a.n_used * a.n_tokens, a.n_expert) * (a.N / 32) >= INT32_MAX) return false;  // (the kernel counts its items in an int)
+    const int64_t nblk = a.K / blk;
+    if ((int64_t) a.n_tokens * a.b_rows * nblk * (int64_t) (mx ? sizeof(q80_dev) : sizeof(q8k_dev)) >= INT32_MAX) return false;  // (the gather's 32-bit lane offsets into the activation area)
+    if (mmid_group_max_tiles((int64_t) a.n_used * a.n_tokens, a.n_expert) * (a.N / 32) >= INT32_MAX) return false;  // (the kernels count their items in an int)
+    if (mx) return a.w_nb1 == nblk * 17;
     if (a.type == GGML_TYPE_Q4_K) return a.w_nb1 == nblk * 144;
     if (a.type == GGML_TYPE_Q5_K) return a.w_nb1 == nblk * 176;
     if (a.type == GGML_TYPE_Q6_K) return a.w_nb1 == nblk * 210 && (a.w_nb1 % 4) == 0 && (a.w_nb2 % 4) == 0 && ((uintptr_t) a.W % 4) == 0;
@@ -302,11 +307,16 @@ bool launch_mmid_grouped(hipStream_t s, const mmid_args & a, void * scratch, siz
         MI_ERR("launch_mmid_grouped: %zu bytes of scratch, %zu needed", scratch_bytes, mmid_group_scratch_bytes(n_pairs, a.n_expert));
         return false;
     }
-    const int max_tiles = (int) mmid_group_max_tiles(n_pairs, a.n_expert);
-    int * const hdr = (int *) scratch;
-    int4 * const tiles = (int4 *) ((char *) scratch + GR_HDR_BYTES);
-    int * const perm = (int *) (tiles + max_tiles);
+    const mmid_group_scratch g = mmid_group_layout(scratch, n_pairs, a.n_expert);
+    int * const hdr = g.hdr;
+    int4 * const tiles = g.tiles;
+    int * const perm = g.perm;
+    const int max_tiles = g.max_tiles;
     hipLaunchKernelGGL(k_mmid_group, dim3(1), dim3(GR_NT), 0, s, a.ids, a.ids_nb1, a.n_used, (int) n_pairs, a.n_expert, hdr, tiles, perm);
+    if (a.type == GGML_TYPE_MXFP4) {
+        launch_mmid_grouped_mxfp4(s, a, g);
+        return true;
+    }
     if (a.type == GGML_TYPE_Q4_K) return launch_grouped_t<4>(s, a, hdr, tiles, perm, max_tiles);
     if (a.type == GGML_TYPE_Q5_K) return launch_grouped_t<5>(s, a, hdr, tiles, perm, max_tiles);
     return launch_grouped_t<6>(s, a, hdr, tiles, perm, max_tiles);

@@ -68,8 +68,8 @@ namespace mi355x {
 // 1: on the matrix cores where the shape is routed there; 0: the dot form everywhere; 2: the matrix cores wherever the operands allow (A/B runs, tests; conv.hip).
 // gn_form (backend_ctx::gn_form, default 0, GGML_MI355X_GN_FORM, set_option("gn_form", 0 / 1 / 2)) likewise: which of GROUP_NORM's two forms serves a node.
 // 0: routed by the group's length; 1: the resident form wherever a group fits it; 2: the split form everywhere (A/B runs, tests; diffusion.hip).
-// mmid_group (backend_ctx::mmid_group, default 1, GGML_MI355X_MMID_GROUP, set_option("mmid_group", 0 / 1 / 2)) likewise: which form serves a MUL_MAT_ID over K-quant experts.
-// 1: the grouped matrix-core form from MI_MMID_GROUP_MIN_PAIRS pairs on; 0: the pair form everywhere; 2: the grouped form from 2 pairs on (A/B runs, tests; mmid_group.hip).
+// mmid_group (backend_ctx::mmid_group, default 1, GGML_MI355X_MMID_GROUP, set_option("mmid_group", 0 / 1 / 2)) likewise: which form serves a MUL_MAT_ID over K-quant or MXFP4 experts.
+// 1: the grouped matrix-core form from MI_MMID_GROUP_MIN_PAIRS (MXFP4: MI_MMID_GROUP_MXFP4_MIN_PAIRS) pairs on; 0: the pair form everywhere; 2: the grouped form from 2 pairs on (A/B runs, tests; mmid_group.hip).
 
 struct options {
 #define MI_X(type, name, def, flag, env) type name = def;

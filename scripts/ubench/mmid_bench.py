@@ -4,7 +4,8 @@ scripts/ubench/mmid_bench.py [type] [n_tokens]` and read the trace with `scripts
 grid size of its own); `--group 0,2` times the node under each value of the backend's mmid_group switch (0: the pair form, 2: the grouped matrix-core form forced on), `--windows 5` takes
 five windows per cell (median, lowest, highest);
 with n_tokens > 1 (the larger-batch form: the same launch over more pairs) the dense yardstick is the batch mat-mul of that matrix
-with n_tokens columns.  The script itself prints the hipEvent-bracketed class times of the backend's timing option as a cross-check."""
+with n_tokens columns.  Type `mxfp4` times the gpt-oss expert shapes instead (K = N = 2880, 4 of 32 and 4 of 128 experts, one activation row a token and one a
+slot), each node with its ADD_ID riding in the store as gpt-oss runs it, and no dense yardstick (no gpt-oss file has a dense MXFP4 matrix).  The script itself prints the hipEvent-bracketed class times of the backend's timing option as a cross-check."""
 import ctypes as C
 import os
 import sys
@@ -19,7 +20,17 @@ import llama_box_amd as L  # noqa: E402
 
 SHAPES = {"mixtral-up": (4096, 14336, 8, 2, False), "mixtral-down": (14336, 4096, 8, 2, True),
           "qwen3-up": (2048, 768, 128, 8, False), "qwen3-down": (768, 2048, 128, 8, True)}
-TYPES = {"q4_K": L.Q4_K, "q5_K": L.Q5_K, "q6_K": L.Q6_K, "q8_0": L.Q8_0}
+GPTOSS_SHAPES = {"oss20b-up": (2880, 2880, 32, 4, False), "oss20b-down": (2880, 2880, 32, 4, True),
+                 "oss120b-up": (2880, 2880, 128, 4, False), "oss120b-down": (2880, 2880, 128, 4, True)}
+TYPES = {"q4_K": L.Q4_K, "q5_K": L.Q5_K, "q6_K": L.Q6_K, "q8_0": L.Q8_0, "mxfp4": L.MXFP4}
+
+
+def mxfp4_experts(K, N, n_expert, rng):
+    """[n_expert, N, K / 32 * 17] random codes, the block exponents around the value that gives a row a trained network's scale (tests/mxfp4_ref.py: rand_blocks)"""
+    W = rng.integers(0, 256, (n_expert, N, K // 32, 17), dtype=np.uint8)
+    e0 = 128 + int(np.round(np.log2(1.0 / (5.85 * np.sqrt(K)))))
+    W[..., 0] = rng.integers(e0 - 2, e0 + 2, W.shape[:3], dtype=np.uint8)
+    return W.reshape(n_expert, N, -1)
 
 
 def run(be, build, reps):
@@ -62,9 +73,11 @@ def main():
     be.set_option("timing", 1)
     H = L.host()
     rng = np.random.default_rng(0)
-    for name, (K, N, n_expert, n_used, per_slot) in SHAPES.items():
+    mx = qtype == L.MXFP4
+    for name, (K, N, n_expert, n_used, per_slot) in (GPTOSS_SHAPES if mx else SHAPES).items():
         row_bytes = K // L.TYPE_BLCK[qtype] * L.TYPE_SIZE[qtype]
-        W = np.stack([T.rand_weight(qtype, K, N, rng) for _ in range(n_expert)])
+        W = mxfp4_experts(K, N, n_expert, rng) if mx else np.stack([T.rand_weight(qtype, K, N, rng) for _ in range(n_expert)])
+        bias = rng.standard_normal((n_expert, N)).astype(np.float32)
         for n_tok in toks:
             reps = 50 if n_tok == 1 else 10
             ids = np.stack([rng.permutation(n_expert)[:n_used] for _ in range(n_tok)]).astype(np.int32)
@@ -75,13 +88,14 @@ def main():
             def moe(g):
                 as_t = g.new(qtype, [K, N, n_expert], W)
                 idt = H.ggml_view_2d(g.ctx, g.new(L.I32, [n_expert, n_tok], full), n_used, n_tok, n_expert * 4, 0)
-                return H.ggml_mul_mat_id(g.ctx, as_t, g.new(L.F32, [K, b.shape[1], n_tok], b), idt)
+                mm = H.ggml_mul_mat_id(g.ctx, as_t, g.new(L.F32, [K, b.shape[1], n_tok], b), idt)
+                return H.ggml_add_id(g.ctx, mm, g.new(L.F32, [N, n_expert], bias), idt) if mx else mm
 
             def dense(g):
                 w = g.new(qtype, [K, n_used * N], W[:n_used].reshape(n_used * N, -1))
                 return H.ggml_mul_mat(g.ctx, w, g.new(L.F32, [K, n_tok], np.ascontiguousarray(b[:, 0])))
 
-            for kind, fn, grp in [("mul_mat_id", moe, g) for g in groups] + [("dense", dense, None)]:
+            for kind, fn, grp in [("mul_mat_id", moe, g) for g in groups] + ([] if mx else [("dense", dense, None)]):
                 if grp is not None:
                     be.set_option("mmid_group", grp)
                 per = {}
@@ -89,7 +103,7 @@ def main():
                     be.timing_report(reset=True)
                     run(be, fn, reps)
                     for cls, (cnt, ms, _) in be.timing_report(reset=True).items():
-                        if cnt and (cls.startswith("mmid") or cls.startswith("mmvq") or cls.startswith("mmq")):
+                        if cnt and (cls.startswith("mmid") or cls == "add_id" or cls.startswith("mmvq") or cls.startswith("mmq")):
                             per.setdefault(cls, []).append(ms * 1e3 / cnt)
                 nbytes = n_used * N * row_bytes
                 for cls, v in sorted(per.items()):
