@@ -213,17 +213,46 @@ bool mm_batched_q_ok(const ggml_tensor * op) {
     return op->ne[0] == a->ne[1] && op->ne[1] == b->ne[1] && op->ne[2] == b->ne[2] && op->ne[3] == b->ne[3];
 }
 
+// FLASH_ATTN_EXT at K 576 / V 512 over one shared KV head (fattn_mla.hip): the node of llama.cpp's deepseek2 graph with -fa.
+//   q    f32 [576, n_q, n_head, nb], nb[0] == 4, nb[1..3] multiples of 16;
+//   k    f16 [576, n_kv, 1, kb], nb[0] == 2, nb[1] and nb[3] multiples of 16;  v f16 [512, n_kv, 1, kb] under the same stride conditions — a tensor of its own or a
+//        view into k's rows (the launcher detects the view: one fetch serves both products);  nb % kb == 0;
+//   mask absent, or f16 [>= n_kv, >= n_q, 1, mb] with contiguous rows and nb % mb == 0;  max_bias == 0, logit_softcap == 0, no sinks;
+//   dst  f32 contiguous [512, n_head, n_q, nb].
+// n_kv, n_q, n_head >= 1.  int indices in the kernel: n_q * n_head (the kernel's rows; the combine pass's grid x) and n_kv up to INT32_MAX / 2; grid z = nb up to 65535.
+// Everything else at these head sizes stays refused: a quantised, bf16 or f32 compressed cache, k->ne[2] != 1, soft-capping, ALiBi, sinks.  The whole contract is
+// here: supports_op, run_node and plan_ws ask nobody else.
+static bool fa_mla_ok(const ggml_tensor * op) {
+    const ggml_tensor * a = op->src[0];
+    const ggml_tensor * k = op->src[1];
+    const ggml_tensor * v = op->src[2];
+    const ggml_tensor * m = op->src[3];
+    if (op->op != GGML_OP_FLASH_ATTN_EXT || !a || !k || !v || op->src[4]) return false;
+    if (a->type != GGML_TYPE_F32 || k->type != GGML_TYPE_F16 || v->type != GGML_TYPE_F16 || op->type != GGML_TYPE_F32) return false;
+    if (a->ne[0] != 576 || k->ne[0] != 576 || v->ne[0] != 512 || k->ne[2] != 1 || v->ne[2] != 1 || v->ne[1] != k->ne[1] || v->ne[3] != k->ne[3]) return false;
+    if (a->nb[0] != 4 || (a->nb[1] % 16) || (a->nb[2] % 16) || (a->nb[3] % 16)) return false;
+    for (const ggml_tensor * t : {k, v})
+        if (t->nb[0] != 2 || (t->nb[1] % 16) || (t->nb[3] % 16)) return false;
+    if (k->ne[1] < 1 || a->ne[1] < 1 || a->ne[2] < 1 || a->ne[3] < 1 || k->ne[3] < 1 || a->ne[3] % k->ne[3] != 0) return false;
+    if (k->ne[1] > INT32_MAX / 2 || a->ne[1] > INT32_MAX / 2 || a->ne[2] > INT32_MAX / 2 || a->ne[1] * a->ne[2] > INT32_MAX / 2 || a->ne[3] > 65535) return false;
+    if (m && (m->type != GGML_TYPE_F16 || !rows_contig(m) || m->ne[0] < k->ne[1] || m->ne[1] < a->ne[1] || m->ne[2] != 1 || m->ne[3] < 1 || a->ne[3] % m->ne[3] != 0)) return false;
+    if (ggml_abi_op_param_f32(op, 1) != 0.0f || ggml_abi_op_param_f32(op, 2) != 0.0f) return false;
+    return ggml_abi_is_contiguous(op) && op->ne[0] == 512 && op->ne[1] == a->ne[2] && op->ne[2] == a->ne[1] && op->ne[3] == a->ne[3];
+}
+
 // which attention path serves this FLASH_ATTN_EXT node: 0 none (the host keeps it on the CPU backend), 1 the f16 kernels on the cache views in place,
 // 2 the lane-parallel kernel on block_q8_0 K / V, 3 the f16 kernels on an f16 IMAGE of whichever of K / V is kept in another type (kv_types.hip:
 // -ctk / -ctv q4_0, q4_1, q5_0, q5_1, iq4_nl, bf16, f32, mixed pairs, and q8_0 shapes route 2 does not take).  Head sizes 64, 128 and 256; 72, 80, 88 and 112 on
 // route 1 only (fattn_hd.hip: none of them is a whole number of 32-value blocks, so llama.cpp offers no block-format cache there; bf16 / f32 stay refused).
-// 96 stays refused: its refusal is pinned by a test.
+// 96 stays refused: its refusal is pinned by a test.  4: K 576 / V 512 over one shared KV head (fa_mla_ok above; fattn_mla.hip), asked before the
+// refusals of unequal head sizes and of more than 8 query heads per KV head.
 static int fa_route(const ggml_tensor * op) {
     const ggml_tensor * a = op->src[0];
     const ggml_tensor * k = op->src[1];
     const ggml_tensor * v = op->src[2];
     const ggml_tensor * m = op->src[3];
     if (!a || !k || !v || a->type != GGML_TYPE_F32) return 0;
+    if (fa_mla_ok(op)) return 4;
     if (k->type == GGML_TYPE_Q8_0 && v->type == GGML_TYPE_Q8_0) {
         // quantised KV cache: served by the lane-parallel kernel (head_dim 128, 1 .. 8 query heads per KV head, no soft-capping / ALiBi)
         const int64_t g = k->ne[2] ? a->ne[2] / k->ne[2] : 0;
@@ -743,6 +772,10 @@ static ws_plan plan_ws(backend_ctx * c, const ggml_cgraph * g) {
             if (c->opt.bf16_preround) p.aux_bytes = std::max(p.aux_bytes, mul_mat_bf16_workspace_bytes(TD(n->src[0]), TD(n->src[1])));
         } else if (n->op == GGML_OP_FLASH_ATTN_EXT) {
             const tdesc q = TD(n->src[0]), k = TD(n->src[1]), v = TD(n->src[2]);
+            if (fa_route(n) == 4) {  // K 576 / V 512: the partial records of fattn_mla.hip, sized by its own chooser
+                p.aux_bytes = std::max(p.aux_bytes, fattn_mla_ws_bytes(q, std::min(64, c->opt.fa_splits > 0 ? c->opt.fa_splits : fattn_mla_pick_splits(q, k))));
+                continue;
+            }
             // (both forms a 33+-token batch may take — matrix-core tiles or, for a mask known to be sparse, position lists — fit this)
             const int ns = std::min(64, c->opt.fa_splits > 0 ? c->opt.fa_splits : std::max(fattn_pick_splits(q, k), 16));
             if (fa_route(n) == 3) {  // the f16 images of K / V behind the largest partial-record area the f16 kernels may ask for
@@ -2806,6 +2839,15 @@ static int run_node(exec_state & st, int i) {
             const ggml_tensor * k = n->src[1];
             const ggml_tensor * v = n->src[2];
             const ggml_tensor * m = n->src[3];
+            if (fa_route(n) == 4) {  // K 576 / V 512 over one shared KV head: no f16 image, position list, visibility scan or fusion applies to this node
+                const tdesc qd = TD(a), kd = TD(k), vd = TD(v), md = m ? TD(m) : qd;
+                const int ns = std::min(64, c->opt.fa_splits > 0 ? c->opt.fa_splits : fattn_mla_pick_splits(qd, kd));
+                timed_scope ts(c, "flash_attn", (double) (k->ne[1] * k->ne[0] * 2));
+                g_fa_form = 0;
+                c->st.kernel_launches += launch_flash_attn_mla(s, qd, kd, vd, m ? &md : nullptr, TD(n), ggml_abi_op_param_f32(n, 0), ns, (char *) c->ws + st.aux_off);
+                c->st.fa_form = g_fa_form;
+                return 1;
+            }
             fattn_params p;
             p.scale = ggml_abi_op_param_f32(n, 0);
             p.max_bias = ggml_abi_op_param_f32(n, 1);

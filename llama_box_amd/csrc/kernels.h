@@ -452,8 +452,8 @@ void launch_flash_attn_combine(hipStream_t s, int D, const float * ws, const flo
 //   bits 17..19 the padded-row head sizes of fattn_hd.hip (FA_FORM_HD_*; bits 12 and 16 are clear then; 0 for every other size: no earlier code moves)
 // (tests/fa_ref.py parses these names and values)
 enum {
-    FA_FORM_K_SPLIT = 1, FA_FORM_K_DEC = 2, FA_FORM_K_MMA = 3,                                    // k_fattn_split / k_fattn_dec128 / k_fattn_mma
-    FA_FORM_MODE_PLAIN = 0, FA_FORM_MODE_SKIP = 1, FA_FORM_MODE_LIST = 2,                         // k_fattn_dec128's MODE; k_fattn_mma: 1 = with tile states
+    FA_FORM_K_SPLIT = 1, FA_FORM_K_DEC = 2, FA_FORM_K_MMA = 3, FA_FORM_K_MLA = 4,                 // k_fattn_split / k_fattn_dec128 / k_fattn_mma / k_fattn_mla
+    FA_FORM_MODE_PLAIN = 0, FA_FORM_MODE_SKIP = 1, FA_FORM_MODE_LIST = 2,                         // k_fattn_dec128's MODE; k_fattn_mma: 1 = with tile states; k_fattn_mla: 1 = v is a view into k
     FA_FORM_KV_F16 = 0, FA_FORM_KV_Q8_0 = 1, FA_FORM_KV_BLOCK = 2, FA_FORM_KV_Q8_IMAGE = 3,       // f16 cache, block_q8_0 in place, another block format in place, q8_0 through its f16 image
     FA_FORM_TAIL_NONE = 0, FA_FORM_TAIL_COMBINE = 1, FA_FORM_TAIL_COMBINE_ROWS = 2, FA_FORM_TAIL_SELF_MERGE = 3, FA_FORM_TAIL_MERGE2 = 4, FA_FORM_TAIL_FAT = 5,
     FA_FORM_D256_BIT = 16,  // the bit (not a field value) that says head size 256
@@ -471,6 +471,12 @@ static inline bool fattn_hd_size(int64_t D) { return D == 72 || D == 80 || D == 
 static inline int fa_form_hd(int64_t D) { return (D == 72 ? FA_FORM_HD_72 : D == 80 ? FA_FORM_HD_80 : D == 88 ? FA_FORM_HD_88 : D == 112 ? FA_FORM_HD_112 : 0) << FA_FORM_HD_SHIFT; }
 void launch_flash_attn_hd(hipStream_t s, const tdesc & q, const tdesc & k, const tdesc & v, const tdesc * mask, const float * sinks, const tdesc & dst, const fattn_params & p, void * workspace);
 void launch_fattn_combine_hd(hipStream_t s, int D, const float * ws, const float * sinks, const tdesc & dst, int n_q, int n_head, int n_batch, int n_splits);
+// ---- K 576 / V 512 over one shared KV head (fattn_mla.hip): DeepSeek's multi-head latent attention with -fa.  Query rows are (token, head) pairs, 64 a workgroup; the
+// contraction and the output are split over the workgroup's four waves.  graph.cpp's fa_mla_ok is the contract; the code is (FA_FORM_K_MLA, mode 1 where v aliases k, 4
+// waves, f16 cache, the head-size bits clear).  The chooser is this kernel's own, and so is the combine pass; the launcher returns the number of launches (1 or 2)
+int fattn_mla_pick_splits(const tdesc & q, const tdesc & k);
+size_t fattn_mla_ws_bytes(const tdesc & q, int n_splits);
+int launch_flash_attn_mla(hipStream_t s, const tdesc & q, const tdesc & k, const tdesc & v, const tdesc * mask, const tdesc & dst, float scale, int n_splits, void * workspace);
 
 // ---- the decode copy (repack.hip): rows [r0, r0 + n_rows) of a K-quant [K, N] matrix from the block layout at `src` into the plane layout at `dst` (same row stride)
 bool repack_supported(int type, int64_t K, int64_t nb1);
@@ -555,6 +561,7 @@ void tu_touch_ops_act(hipStream_t s);
 void tu_touch_fattn(hipStream_t s);
 void tu_touch_fattn_mma(hipStream_t s);
 void tu_touch_fattn_hd(hipStream_t s);
+void tu_touch_fattn_mla(hipStream_t s);
 void tu_touch_tp_p2p(hipStream_t s);
 void tu_touch_kv_types(hipStream_t s);
 void tu_touch_repack(hipStream_t s);
@@ -588,6 +595,7 @@ inline void preload_kernel_files(hipStream_t s) {
     tu_touch_fattn(s);
     tu_touch_fattn_mma(s);
     tu_touch_fattn_hd(s);
+    tu_touch_fattn_mla(s);
     tu_touch_tp_p2p(s);
     tu_touch_ssm(s);
     tu_touch_rwkv(s);
