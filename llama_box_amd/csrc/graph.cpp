@@ -2992,8 +2992,10 @@ static int run_node(exec_state & st, int i) {
         }
         case GGML_OP_SSM_SCAN: {
             // (bytes: the states read and written; x, dt, B, C and y are small beside them at decode)
-            timed_scope ts(c, "ssm_scan", (double) (ggml_abi_nelements(n) - ggml_abi_nelements(b)) * 8);
-            if (!launch_ssm_scan(s, TD(a), TD(b), TD(n->src[2]), TD(n->src[3]), TD(n->src[4]), TD(n->src[5]), TD(n->src[6]), TD(n))) return -1;
+            // the chunked matrix-core form for prompt batches of the Mamba-2 form (ssm_chunk.hip; it needs no scratch, so plan_ws has nothing to size)
+            const bool chunked = ssm_scan_runs_chunked(TD(a), TD(b), TD(n->src[3]), c->ssm_chunk);
+            timed_scope ts(c, chunked ? "ssm_scan_chunk" : "ssm_scan", (double) (ggml_abi_nelements(n) - ggml_abi_nelements(b)) * 8);
+            if (!(chunked ? launch_ssm_scan_chunk : launch_ssm_scan)(s, TD(a), TD(b), TD(n->src[2]), TD(n->src[3]), TD(n->src[4]), TD(n->src[5]), TD(n->src[6]), TD(n))) return -1;
             c->st.kernel_launches++;
             return 1;
         }

@@ -491,6 +491,15 @@ bool launch_concat(hipStream_t s, const tdesc & a, const tdesc & b, const tdesc 
 bool launch_ssm_conv(hipStream_t s, const tdesc & sx, const tdesc & c, const tdesc & dst, const float * bias);
 // SSM_SCAN, d_state 16 / 64 / 128 / 256, n_group 1 or n_head; dst: y, then the final states in sequence order
 bool launch_ssm_scan(hipStream_t s, const tdesc & st, const tdesc & x, const tdesc & dt, const tdesc & A, const tdesc & B, const tdesc & C, const tdesc & ids, const tdesc & dst);
+// SSM_SCAN, the chunked matrix-core form (ssm_chunk.hip): A per head, d_state 64 / 128, any head_dim and token count; the same operands and result.
+// ssm_scan_runs_chunked is THE form choice, mode being the ssm_chunk switch (0 serial everywhere, 1 routed, 2 chunked wherever the operands allow):
+//   MI_SSM_CHUNK_MIN_TOKENS    routed: the chunked form from this many tokens a sequence on.  Never below 128: shorter nodes (decode steps, captured graphs, every
+//                              shape of tests/test_gpu_ssm.py) keep the serial kernel and its bits.  DESIGN.md 4i holds the measured table behind the value
+//   MI_SSM_CHUNK_MIN_HEAD_DIM  routed: only heads of at least this many rows (a wave owns 16 rows of a 64-row tile; narrower heads leave waves idle and were not measured)
+#define MI_SSM_CHUNK_MIN_TOKENS 128
+#define MI_SSM_CHUNK_MIN_HEAD_DIM 32
+bool ssm_scan_runs_chunked(const tdesc & st, const tdesc & x, const tdesc & A, int mode);
+bool launch_ssm_scan_chunk(hipStream_t s, const tdesc & st, const tdesc & x, const tdesc & dt, const tdesc & A, const tdesc & B, const tdesc & C, const tdesc & ids, const tdesc & dst);
 
 // ---- linear-attention recurrent layers (rwkv.hip): f32, head size 64 / 128, per-token operands [S, H, T] contiguous, the state S * S * H floats a
 // sequence, dst = y [S * H, T] then the new states.  The three recurrences return false at a shape supports_op refuses (graph.cpp: rwkv_wkv_ok)
@@ -570,6 +579,7 @@ void tu_touch_mmid_group(hipStream_t s);
 void tu_touch_mmid_group_mxfp4(hipStream_t s);
 void tu_touch_mmb(hipStream_t s);
 void tu_touch_ssm(hipStream_t s);
+void tu_touch_ssm_chunk(hipStream_t s);
 void tu_touch_rwkv(hipStream_t s);
 void tu_touch_conv(hipStream_t s);
 void tu_touch_diffusion(hipStream_t s);
@@ -598,6 +608,7 @@ inline void preload_kernel_files(hipStream_t s) {
     tu_touch_fattn_mla(s);
     tu_touch_tp_p2p(s);
     tu_touch_ssm(s);
+    tu_touch_ssm_chunk(s);
     tu_touch_rwkv(s);
     tu_touch_conv(s);
     tu_touch_diffusion(s);

@@ -2,6 +2,8 @@
 over that time, as a share of 8 TB/s.
 
     python scripts/ubench/ssm_bench.py                       every shape, warm and cold: host clock around synchronised windows, then the hipEvent class times
+    python scripts/ubench/ssm_bench.py chunk                 the Mamba-2 prompt shapes only, each under ssm_chunk 0 (k_ssm_scan, the serial kernel) and 2 (the chunked
+                                                             matrix-core form of csrc/ssm_chunk.hip), the two forms alternating twice
     rocprofv3 --kernel-trace --stats --output-format csv -d DIR -o ssm -- python scripts/ubench/ssm_bench.py SHAPE MODE
                                                              one shape in one mode (warm | cold), no events: kernel times are the trace's (scripts/trace_by_grid.py)
 
@@ -27,7 +29,10 @@ PEAK = 8.0e12  # bytes / s
 SCAN = {
     "m2-decode-s1": (128, 64, 80, 1, 1, 1, False),
     "m2-decode-s32": (128, 64, 80, 1, 1, 32, False),
+    "m2-prompt-128": (128, 64, 80, 1, 128, 1, False),
     "m2-prompt-512": (128, 64, 80, 1, 512, 1, False),
+    "m2-prompt-2048": (128, 64, 80, 1, 2048, 1, False),
+    "m2-prompt-s32x128": (128, 64, 80, 1, 128, 32, False),
     "m1-decode-s1": (16, 1, 5120, 1, 1, 1, True),
     "m1-decode-s32": (16, 1, 5120, 1, 1, 32, True),
     "m1-prompt-512": (16, 1, 5120, 1, 512, 1, True),
@@ -64,8 +69,13 @@ def build_conv(g, rng, d_conv, cd, n_t, n_s):
     return H.ggml_silu(g.ctx, H.ggml_add(g.ctx, H.ggml_ssm_conv(g.ctx, sx, c), b))
 
 
-def measure(be, name, mode, events):
+CHUNK_SHAPES = ("m2-prompt-128", "m2-prompt-512", "m2-prompt-2048", "m2-prompt-s32x128")
+
+
+def measure(be, name, mode, events, chunk=None):
+    """chunk: the ssm_chunk switch for this measurement (None: the routed default)."""
     H = L.host()
+    be.set_option("ssm_chunk", 1 if chunk is None else chunk)
     scan = name in SCAN
     shape = SCAN[name] if scan else CONV[name]
     nbytes = scan_bytes(*shape) if scan else conv_bytes(*shape)
@@ -94,7 +104,8 @@ def measure(be, name, mode, events):
             assert H.ggml_backend_graph_compute(be.backend, gf) == 0
         be.synchronize()
         wall_us = (time.perf_counter() - t0) * 1e6 / (reps * copies)
-        line = f"{name:15s} {mode:4s} copies={copies:3d} launches={reps * copies:5d} {nbytes / 1e6:8.2f} MB/launch  host clock {wall_us:8.2f} us/launch ({nbytes / wall_us / 1e6 / (PEAK / 1e12) * 100:5.1f} % of 8 TB/s)"
+        form = "" if chunk is None else (" serial " if chunk == 0 else " chunked")
+        line = f"{name + form:25s} {mode:4s} copies={copies:3d} launches={reps * copies:5d} {nbytes / 1e6:8.2f} MB/launch  host clock {wall_us:8.2f} us/launch ({nbytes / wall_us / 1e6 / (PEAK / 1e12) * 100:5.1f} % of 8 TB/s)"
         if events:
             be.set_option("timing", 1)
             be.timing_report(reset=True)
@@ -109,12 +120,18 @@ def measure(be, name, mode, events):
         print(line, flush=True)
     finally:
         g.free()
+        be.set_option("ssm_chunk", 1)
 
 
 def main():
     be = L.Backend(0)
     be.set_option("graphs", 0)
-    if len(sys.argv) > 2:
+    if len(sys.argv) == 2 and sys.argv[1] == "chunk":
+        for name in CHUNK_SHAPES:
+            for mode in ("warm", "cold"):
+                for chunk in (0, 2, 0, 2):
+                    measure(be, name, mode, events=True, chunk=chunk)
+    elif len(sys.argv) > 2:
         measure(be, sys.argv[1], sys.argv[2], events=False)
     else:
         for name in list(SCAN) + list(CONV):
