@@ -730,6 +730,7 @@ static ggml_backend_t dev_init_backend(ggml_backend_dev_t dev, const char *) {
     c->gn_form = std::max(0, std::min(2, env_int("GGML_MI355X_GN_FORM", 0)));
     c->mmid_group = std::max(0, std::min(2, env_int("GGML_MI355X_MMID_GROUP", 1)));
     c->ssm_chunk = std::max(0, std::min(2, env_int("GGML_MI355X_SSM_CHUNK", 1)));
+    c->wkv_chunk = std::max(0, std::min(2, env_int("GGML_MI355X_WKV_CHUNK", 1)));
     if (hipMalloc((void **) &c->ss_buf, 256 * sizeof(double)) != hipSuccess) {  // (optional: without it every norm prologue sums its own row)
         (void) hipGetLastError();
         c->ss_buf = nullptr;
@@ -838,6 +839,7 @@ static int api_set_option(ggml_backend_t be, const char * key, const char * valu
         else if (k == "gn_form") { if (v < 0 || v > 2) return -2; c->gn_form = v; }
         else if (k == "mmid_group") { if (v < 0 || v > 2) return -2; c->mmid_group = v; }
         else if (k == "ssm_chunk") { if (v < 0 || v > 2) return -2; c->ssm_chunk = v; }
+        else if (k == "wkv_chunk") { if (v < 0 || v > 2) return -2; c->wkv_chunk = v; }
         else return -1;
     }
     HIP_SOFT(hipStreamSynchronize(c->stream));

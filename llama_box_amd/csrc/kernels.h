@@ -506,6 +506,17 @@ bool launch_ssm_scan_chunk(hipStream_t s, const tdesc & st, const tdesc & x, con
 bool launch_rwkv_wkv6(hipStream_t s, const tdesc & k, const tdesc & v, const tdesc & r, const tdesc & tf, const tdesc & td, const tdesc & state, const tdesc & dst);
 bool launch_gated_linear_attn(hipStream_t s, const tdesc & k, const tdesc & v, const tdesc & q, const tdesc & g, const tdesc & state, const tdesc & dst, float scale);
 bool launch_rwkv_wkv7(hipStream_t s, const tdesc & r, const tdesc & w, const tdesc & k, const tdesc & v, const tdesc & a, const tdesc & b, const tdesc & state, const tdesc & dst);
+// RWKV_WKV6 / GATED_LINEAR_ATTN, the chunked matrix-core form (wkv_chunk.hip): the same operands and result, any token count.  wkv_runs_chunked is THE form choice,
+// mode being the wkv_chunk switch (0 serial everywhere, 1 routed, 2 chunked wherever the operands allow); k is the k operand, state the state operand:
+//   MI_WKV_CHUNK_MIN_TOKENS  routed: the chunked form from this many tokens a sequence on.  Never below 128: shorter nodes (decode steps, captured step graphs, every
+//                            shape of tests/test_gpu_rwkv.py) keep the serial kernel and its bits.  DESIGN.md 4k holds the measured table behind the value
+//   MI_WKV_CHUNK_WAVES       waves a workgroup: 4, a 64-column tile whose waves share the construction of A.  1 (a 16-column tile, four times the workgroups, every wave
+//                            rebuilding A) measured 1.7 - 2.3 times slower at one sequence of 40 / 64 heads and lost to the serial kernel (LAB_NOTES.md)
+#define MI_WKV_CHUNK_MIN_TOKENS 128
+#define MI_WKV_CHUNK_WAVES 4
+bool wkv_runs_chunked(const tdesc & k, const tdesc & state, int mode);
+bool launch_rwkv_wkv6_chunk(hipStream_t s, const tdesc & k, const tdesc & v, const tdesc & r, const tdesc & tf, const tdesc & td, const tdesc & state, const tdesc & dst);
+bool launch_gated_linear_attn_chunk(hipStream_t s, const tdesc & k, const tdesc & v, const tdesc & q, const tdesc & g, const tdesc & state, const tdesc & dst, float scale);
 // L2_NORM: y = x / max(sqrt(sum x^2), eps) per row, rows at any strides (nb0 = 4); SQR: contiguous; REPEAT: dst contiguous, src with any element-aligned strides
 void launch_l2_norm(hipStream_t s, const tdesc & src, const tdesc & dst, float eps);
 void launch_sqr(hipStream_t s, const tdesc & src, const tdesc & dst);
@@ -581,6 +592,7 @@ void tu_touch_mmb(hipStream_t s);
 void tu_touch_ssm(hipStream_t s);
 void tu_touch_ssm_chunk(hipStream_t s);
 void tu_touch_rwkv(hipStream_t s);
+void tu_touch_wkv_chunk(hipStream_t s);
 void tu_touch_conv(hipStream_t s);
 void tu_touch_diffusion(hipStream_t s);
 inline void preload_kernel_files(hipStream_t s) {
@@ -610,6 +622,7 @@ inline void preload_kernel_files(hipStream_t s) {
     tu_touch_ssm(s);
     tu_touch_ssm_chunk(s);
     tu_touch_rwkv(s);
+    tu_touch_wkv_chunk(s);
     tu_touch_conv(s);
     tu_touch_diffusion(s);
 }

@@ -4,6 +4,9 @@ write) and that over the time as a share of 8 TB/s.
     python scripts/ubench/rwkv_bench.py                 every op, model and shape: one child process per (op, model, shape) under its own `timeout`, warm then
                                                         cold; the run ends at the first child that fails or runs out of time
     python scripts/ubench/rwkv_bench.py OP MODEL SHAPE  that one case in this process
+    python scripts/ubench/rwkv_bench.py chunk           WKV6 and GLA at the prompt shapes, each under wkv_chunk 0 (k_rwkv_wkv6, the serial kernel) and 2 (the chunked
+                                                        matrix-core form of csrc/wkv_chunk.hip), the two forms alternating three times, warm and cold
+    python scripts/ubench/rwkv_bench.py sweep           the same A/B over token counts from 128 upward, warm: what MI_WKV_CHUNK_MIN_TOKENS rests on
 
 warm: one operand set, launched again and again (a one-sequence state of 1 - 2.6 MB stays in the L2 / the 256 MiB Infinity Cache).  cold: `copies` operand sets of
 more than 512 MiB together, one launch each per graph, so that no launch finds its state in a cache.  Every case is warmed up before its timed window; a
@@ -26,6 +29,8 @@ import llama_box_amd as L  # noqa: E402
 PEAK = 8.0e12  # bytes / s
 MODELS = {"rwkv6-7b": (64, 64), "rwkv7-2.9b": (40, 64), "qrwkv6-32b": (40, 128)}  # (heads, head size)
 SHAPES = {"decode-s1": (1, 1), "decode-s32": (32, 1), "prompt-512": (1, 512)}    # (n_seqs, n_t)
+CHUNK_SHAPES = {"prompt-512": (1, 512), "prompt-2048": (1, 2048)}
+SWEEP_SHAPES = {f"prompt-{n}": (1, n) for n in (128, 192, 256, 384)}
 OPS = {"wkv6": "rwkv_wkv6", "gla": "gated_linear_attn", "wkv7": "rwkv_wkv7"}      # the backend's timing class
 CHILD_TIMEOUT_S = 120
 
@@ -49,10 +54,14 @@ def build(g, rng, op, nh, S, n_seqs, n_t):
     return H.ggml_rwkv_wkv7(g.ctx, r, w, k, v, tok(0.5 / np.sqrt(S)), tok(0.5 / np.sqrt(S)), state)
 
 
-def measure(be, op, model, shape, mode):
+def measure(be, op, model, shape, mode, chunk=None):
+    """chunk: the wkv_chunk switch for this measurement (None: the routed default)."""
     H = L.host()
     nh, S = MODELS[model]
-    n_seqs, n_t = SHAPES[shape]
+    n_seqs, n_t = {**SHAPES, **CHUNK_SHAPES, **SWEEP_SHAPES}[shape]
+    if chunk is not None:
+        be.set_option("wkv_chunk", chunk)
+    form = "" if chunk is None else (" serial " if chunk == 0 else " chunked")
     nbytes = 2 * 4 * S * S * nh * n_seqs  # the states, read once and written once
     footprint = nbytes + 4 * S * nh * n_seqs * n_t * (7 if op == "wkv7" else 5)  # ... and the per-token operands and y: what a copy keeps out of the caches
     copies = 1 if mode == "warm" else max(2, min(256, -(-(512 << 20) // footprint)))
@@ -77,7 +86,7 @@ def measure(be, op, model, shape, mode):
             assert H.ggml_backend_graph_compute(be.backend, gf) == 0
         be.synchronize()
         wall_us = (time.perf_counter() - t0) * 1e6 / (reps * copies)
-        line = (f"{op:5s} {model:11s} {shape:11s} {mode:4s} copies={copies:3d} launches={reps * copies:5d} state {nbytes / 1e6:8.2f} MB/launch  "
+        line = (f"{op:5s} {model:11s} {shape + form:19s} {mode:4s} copies={copies:3d} launches={reps * copies:5d} state {nbytes / 1e6:8.2f} MB/launch  "
                 f"host clock {wall_us:9.2f} us/launch ({nbytes / wall_us / 1e6 / (PEAK / 1e12) * 100:5.1f} % of 8 TB/s)")
         be.set_option("timing", 1)
         be.timing_report(reset=True)
@@ -85,13 +94,14 @@ def measure(be, op, model, shape, mode):
             assert H.ggml_backend_graph_compute(be.backend, gf) == 0
         be.synchronize()
         for cls, (cnt, ms, _) in sorted(be.timing_report(reset=True).items()):
-            if cnt and cls == OPS[op]:
+            if cnt and cls in (OPS[op], OPS[op] + "_chunk"):
                 us = ms * 1e3 / cnt
                 line += f" | events n={cnt} {us:9.2f} us ({nbytes / us / 1e6 / (PEAK / 1e12) * 100:5.1f} %)"
         be.set_option("timing", 0)
         print(line, flush=True)
     finally:
         g.free()
+        be.set_option("wkv_chunk", 1)
 
 
 def main():
@@ -100,6 +110,17 @@ def main():
         be.set_option("graphs", 0)
         for mode in ("warm", "cold"):
             measure(be, sys.argv[1], sys.argv[2], sys.argv[3], mode)
+        be.close()
+        return 0
+    if len(sys.argv) == 2 and sys.argv[1] in ("chunk", "sweep"):
+        be = L.Backend(0)
+        be.set_option("graphs", 0)
+        for model in ("rwkv6-7b", "qrwkv6-32b"):
+            for op in ("wkv6", "gla"):
+                for shape in (CHUNK_SHAPES if sys.argv[1] == "chunk" else SWEEP_SHAPES):
+                    for mode in (("warm", "cold") if sys.argv[1] == "chunk" else ("warm",)):
+                        for chunk in (0, 2) * (3 if sys.argv[1] == "chunk" else 2):
+                            measure(be, op, model, shape, mode, chunk=chunk)
         be.close()
         return 0
     for op, model in (("wkv6", "rwkv6-7b"), ("gla", "rwkv6-7b"), ("wkv7", "rwkv7-2.9b"), ("wkv6", "qrwkv6-32b"), ("gla", "qrwkv6-32b"), ("wkv7", "qrwkv6-32b"),
