@@ -103,7 +103,7 @@ typedef int64_t (*ggml_backend_mi355x_decode_copy_read_t)(ggml_backend_t backend
  * "gn_form" (GROUP_NORM: 0 routed by the group's length, 1 the resident form wherever a group fits it, 2 the split form everywhere; GGML_MI355X_GN_FORM),
  * "mmid_group" (MUL_MAT_ID over Q4_K / Q5_K / Q6_K or MXFP4 experts: 0 the pair form everywhere, 1 the grouped matrix-core form from MI_MMID_GROUP_MIN_PAIRS (MXFP4: MI_MMID_GROUP_MXFP4_MIN_PAIRS) pairs on, 2 from 2 pairs on; GGML_MI355X_MMID_GROUP),
  * "ssm_chunk" (SSM_SCAN with one A per head, d_state 64 / 128: 0 the serial kernel everywhere, 1 the chunked matrix-core form from MI_SSM_CHUNK_MIN_TOKENS tokens a sequence on, 2 wherever the operands allow; GGML_MI355X_SSM_CHUNK),
- * "wkv_chunk" (RWKV_WKV6 / GATED_LINEAR_ATTN: 0 the serial kernel everywhere, 1 the chunked matrix-core form from MI_WKV_CHUNK_MIN_TOKENS tokens a sequence on, 2 wherever the operands allow; GGML_MI355X_WKV_CHUNK),
+ * "wkv_chunk" (RWKV_WKV6 / GATED_LINEAR_ATTN / RWKV_WKV7: 0 the serial kernel everywhere, 1 the chunked matrix-core form from MI_WKV_CHUNK_MIN_TOKENS (RWKV_WKV7: MI_WKV7_CHUNK_MIN_TOKENS) tokens a sequence on, 2 wherever the operands allow; GGML_MI355X_WKV_CHUNK),
  * "mmid_bias" (an ADD_ID directly behind its MUL_MAT_ID — the per-expert bias of a gpt-oss expert block — rides in that launch's store; default 1, GGML_MI355X_MMID_BIAS). */
 typedef int (*ggml_backend_mi355x_set_option_t)(ggml_backend_t backend, const char * key, const char * value);
 /* Counters for tests/bench: "graph_launches", "graph_captures", "graph_early_captures", "graph_shadow_captures", "graph_capture_walk_ns", "graph_exec_update_ns", "graph_shadow_eager_ns", "graph_exec_updates", "eager_graphs", "kernel_launches", "fused_nodes",

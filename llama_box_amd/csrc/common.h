@@ -162,7 +162,7 @@ struct backend_ctx {
     int mmid_group = 1;        // MUL_MAT_ID over K-quant or MXFP4 experts: 1 = the grouped matrix-core form from MI_MMID_GROUP_MIN_PAIRS (MXFP4: MI_MMID_GROUP_MXFP4_MIN_PAIRS) pairs on (graph.cpp: mmid_runs_grouped), 0 = the pair form everywhere, 2 = the grouped form wherever the operands allow, from 2 pairs on (set_option "mmid_group" / GGML_MI355X_MMID_GROUP; beside the table as ssm_fuse is)
     int gn_form = 0;           // GROUP_NORM: 0 = routed (diffusion.hip: group_norm_runs_resident), 1 = the resident form wherever a group fits it, 2 = the split form everywhere (set_option "gn_form" / GGML_MI355X_GN_FORM; beside the table as ssm_fuse is)
     int ssm_chunk = 1;         // SSM_SCAN in the Mamba-2 form: 1 = the chunked matrix-core form where the node is routed there (ssm_chunk.hip: ssm_scan_runs_chunked, from MI_SSM_CHUNK_MIN_TOKENS tokens on), 0 = the serial kernel everywhere, 2 = the chunked form wherever the operands allow (set_option "ssm_chunk" / GGML_MI355X_SSM_CHUNK; beside the table as ssm_fuse is)
-    int wkv_chunk = 1;         // RWKV_WKV6 / GATED_LINEAR_ATTN: 1 = the chunked matrix-core form where the node is routed there (wkv_chunk.hip: wkv_runs_chunked, from MI_WKV_CHUNK_MIN_TOKENS tokens a sequence on), 0 = the serial kernel everywhere, 2 = the chunked form wherever the operands allow (set_option "wkv_chunk" / GGML_MI355X_WKV_CHUNK; beside the table as ssm_fuse is)
+    int wkv_chunk = 1;         // RWKV_WKV6 / GATED_LINEAR_ATTN / RWKV_WKV7: 1 = the chunked matrix-core form where the node is routed there (wkv_chunk.hip: wkv_runs_chunked, from MI_WKV_CHUNK_MIN_TOKENS tokens a sequence on; wkv7_chunk.hip: wkv7_runs_chunked, from MI_WKV7_CHUNK_MIN_TOKENS), 0 = the serial kernel everywhere, 2 = the chunked form wherever the operands allow (set_option "wkv_chunk" / GGML_MI355X_WKV_CHUNK; beside the table as ssm_fuse is)
     bool mmid_bias = true;     // MUL_MAT_ID -> ADD_ID as one launch, the bias in the store (set_option "mmid_bias" / GGML_MI355X_MMID_BIAS; kept beside the table as ssm_fuse is)
     bool mm_q5_major = false;  // the graph being planned / run holds more Q5_K than Q4_K weight bytes (graph.cpp: mmq_min_cols_for)
     // tensor parallel

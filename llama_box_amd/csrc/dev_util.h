@@ -29,6 +29,7 @@ template <int CTRL> __device__ __forceinline__ double dpp_f64(const double v) {
 #define MI_DPP_QUAD_XOR1 0xB1  /* quad_perm [1,0,3,2] */
 #define MI_DPP_QUAD_XOR2 0x4E  /* quad_perm [2,3,0,1] */
 #define MI_DPP_HALF_MIRROR 0x141
+#define MI_DPP_ROW_MIRROR 0x140
 
 __device__ __forceinline__ float readlane_f32(const float v, const int lane) {
     return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), lane));

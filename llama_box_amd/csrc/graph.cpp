@@ -3003,13 +3003,14 @@ static int run_node(exec_state & st, int i) {
             if (!rwkv_wkv_ok(n)) { MI_ERR("graph_compute: node %d '%s' is outside the recurrent ops' contract (DESIGN.md 4k)", i, n->name); return -1; }
             // (bytes: the states read and written; the per-token operands and y are small beside them at decode)
             const ggml_tensor * const * r = n->src;
-            // the chunked matrix-core form for prompt batches of WKV6 and GLA (wkv_chunk.hip; no scratch, so plan_ws has nothing to size); WKV7 has none
-            const bool chunked = n->op != GGML_OP_RWKV_WKV7 && wkv_runs_chunked(TD(r[0]), TD(r[n->op == GGML_OP_RWKV_WKV6 ? 5 : 4]), c->wkv_chunk);
-            timed_scope ts(c, n->op == GGML_OP_RWKV_WKV6 ? (chunked ? "rwkv_wkv6_chunk" : "rwkv_wkv6") : n->op == GGML_OP_RWKV_WKV7 ? "rwkv_wkv7" : chunked ? "gated_linear_attn_chunk" : "gated_linear_attn",
+            // the chunked matrix-core forms for prompt batches (wkv_chunk.hip, wkv7_chunk.hip; no scratch, so plan_ws has nothing to size)
+            const bool chunked = n->op == GGML_OP_RWKV_WKV7 ? wkv7_runs_chunked(TD(r[0]), TD(r[6]), c->wkv_chunk)
+                                                            : wkv_runs_chunked(TD(r[0]), TD(r[n->op == GGML_OP_RWKV_WKV6 ? 5 : 4]), c->wkv_chunk);
+            timed_scope ts(c, n->op == GGML_OP_RWKV_WKV6 ? (chunked ? "rwkv_wkv6_chunk" : "rwkv_wkv6") : n->op == GGML_OP_RWKV_WKV7 ? (chunked ? "rwkv_wkv7_chunk" : "rwkv_wkv7") : chunked ? "gated_linear_attn_chunk" : "gated_linear_attn",
                            (double) (ggml_abi_nelements(n) - ggml_abi_nelements(a)) * 8);
             bool ok;
             if (n->op == GGML_OP_RWKV_WKV6) ok = (chunked ? launch_rwkv_wkv6_chunk : launch_rwkv_wkv6)(s, TD(r[0]), TD(r[1]), TD(r[2]), TD(r[3]), TD(r[4]), TD(r[5]), TD(n));
-            else if (n->op == GGML_OP_RWKV_WKV7) ok = launch_rwkv_wkv7(s, TD(r[0]), TD(r[1]), TD(r[2]), TD(r[3]), TD(r[4]), TD(r[5]), TD(r[6]), TD(n));
+            else if (n->op == GGML_OP_RWKV_WKV7) ok = (chunked ? launch_rwkv_wkv7_chunk : launch_rwkv_wkv7)(s, TD(r[0]), TD(r[1]), TD(r[2]), TD(r[3]), TD(r[4]), TD(r[5]), TD(r[6]), TD(n));
             else ok = (chunked ? launch_gated_linear_attn_chunk : launch_gated_linear_attn)(s, TD(r[0]), TD(r[1]), TD(r[2]), TD(r[3]), TD(r[4]), TD(n), ggml_abi_op_param_f32(n, 0));
             if (!ok) return -1;
             c->st.kernel_launches++;

@@ -517,6 +517,20 @@ bool launch_rwkv_wkv7(hipStream_t s, const tdesc & r, const tdesc & w, const tde
 bool wkv_runs_chunked(const tdesc & k, const tdesc & state, int mode);
 bool launch_rwkv_wkv6_chunk(hipStream_t s, const tdesc & k, const tdesc & v, const tdesc & r, const tdesc & tf, const tdesc & td, const tdesc & state, const tdesc & dst);
 bool launch_gated_linear_attn_chunk(hipStream_t s, const tdesc & k, const tdesc & v, const tdesc & q, const tdesc & g, const tdesc & state, const tdesc & dst, float scale);
+// RWKV_WKV7, the chunked matrix-core form (wkv7_chunk.hip): the same operands and result, any token count.  wkv7_runs_chunked is THE form choice under the same
+// wkv_chunk switch; r is the r operand, state the state operand:
+//   MI_WKV7_CHUNK_MIN_TOKENS  routed: the chunked form from this many tokens a sequence on, never below 128 (as above).  The sweep (scripts/ubench/rwkv_bench.py sweep
+//                             wkv7, one sequence, warm, serial / chunked us, the repeats within 0.3 us; profiles/wkv7_chunk_ubench.txt): 40 heads of 64: 92.1 / 66.1 at
+//                             128 tokens, 142.9 / 95.6 at 192, 188.8 / 125.9 at 256, 280.9 / 185.4 at 384; 40 heads of 128: 157.4 / 98.0, 228.7 / 142.5, 307.2 / 186.3,
+//                             460.6 / 275.0.  The chunked form wins from the smallest swept count at both head sizes: one constant, 128
+//   MI_WKV7_CHUNK_WAVES       waves a workgroup: 4, a tile of 64 value rows whose waves share the walk that forms the four A matrices.  2 and 1 (every workgroup of a
+//                             head repeating the walk) measured 300 / 435 us against 249 at 512 tokens of 40 heads of 64 and 507 / 876 against 362 at 40 heads of
+//                             128, where 1 loses to the serial kernel (LAB_NOTES.md)
+#define MI_WKV7_CHUNK_MIN_TOKENS 128
+#define MI_WKV7_CHUNK_WAVES 4
+bool wkv7_runs_chunked(const tdesc & r, const tdesc & state, int mode);
+bool launch_rwkv_wkv7_chunk(hipStream_t s, const tdesc & r, const tdesc & w, const tdesc & k, const tdesc & v, const tdesc & a, const tdesc & b, const tdesc & state,
+                            const tdesc & dst);
 // L2_NORM: y = x / max(sqrt(sum x^2), eps) per row, rows at any strides (nb0 = 4); SQR: contiguous; REPEAT: dst contiguous, src with any element-aligned strides
 void launch_l2_norm(hipStream_t s, const tdesc & src, const tdesc & dst, float eps);
 void launch_sqr(hipStream_t s, const tdesc & src, const tdesc & dst);
@@ -593,6 +607,7 @@ void tu_touch_ssm(hipStream_t s);
 void tu_touch_ssm_chunk(hipStream_t s);
 void tu_touch_rwkv(hipStream_t s);
 void tu_touch_wkv_chunk(hipStream_t s);
+void tu_touch_wkv7_chunk(hipStream_t s);
 void tu_touch_conv(hipStream_t s);
 void tu_touch_diffusion(hipStream_t s);
 inline void preload_kernel_files(hipStream_t s) {
@@ -623,6 +638,7 @@ inline void preload_kernel_files(hipStream_t s) {
     tu_touch_ssm_chunk(s);
     tu_touch_rwkv(s);
     tu_touch_wkv_chunk(s);
+    tu_touch_wkv7_chunk(s);
     tu_touch_conv(s);
     tu_touch_diffusion(s);
 }

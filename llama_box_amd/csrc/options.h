@@ -72,7 +72,7 @@ namespace mi355x {
 // 1: the grouped matrix-core form from MI_MMID_GROUP_MIN_PAIRS (MXFP4: MI_MMID_GROUP_MXFP4_MIN_PAIRS) pairs on; 0: the pair form everywhere; 2: the grouped form from 2 pairs on (A/B runs, tests; mmid_group.hip).
 // ssm_chunk (backend_ctx::ssm_chunk, default 1, GGML_MI355X_SSM_CHUNK, set_option("ssm_chunk", 0 / 1 / 2)) likewise: which kernel serves an SSM_SCAN in the Mamba-2 form.
 // 1: the chunked matrix-core form from MI_SSM_CHUNK_MIN_TOKENS tokens a sequence on; 0: the serial kernel everywhere; 2: the chunked form wherever the operands allow (A/B runs, tests; ssm_chunk.hip).
-// wkv_chunk (backend_ctx::wkv_chunk, default 1, GGML_MI355X_WKV_CHUNK, set_option("wkv_chunk", 0 / 1 / 2)) likewise for RWKV_WKV6 and GATED_LINEAR_ATTN: 1 the chunked form from MI_WKV_CHUNK_MIN_TOKENS tokens a sequence on; 0 the serial kernel everywhere; 2 the chunked form wherever the operands allow (wkv_chunk.hip).
+// wkv_chunk (backend_ctx::wkv_chunk, default 1, GGML_MI355X_WKV_CHUNK, set_option("wkv_chunk", 0 / 1 / 2)) likewise for RWKV_WKV6, GATED_LINEAR_ATTN and RWKV_WKV7: 1 the chunked form from MI_WKV_CHUNK_MIN_TOKENS (RWKV_WKV7: MI_WKV7_CHUNK_MIN_TOKENS) tokens a sequence on; 0 the serial kernel everywhere; 2 the chunked form wherever the operands allow (wkv_chunk.hip, wkv7_chunk.hip).
 
 struct options {
 #define MI_X(type, name, def, flag, env) type name = def;

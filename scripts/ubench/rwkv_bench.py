@@ -4,9 +4,11 @@ write) and that over the time as a share of 8 TB/s.
     python scripts/ubench/rwkv_bench.py                 every op, model and shape: one child process per (op, model, shape) under its own `timeout`, warm then
                                                         cold; the run ends at the first child that fails or runs out of time
     python scripts/ubench/rwkv_bench.py OP MODEL SHAPE  that one case in this process
-    python scripts/ubench/rwkv_bench.py chunk           WKV6 and GLA at the prompt shapes, each under wkv_chunk 0 (k_rwkv_wkv6, the serial kernel) and 2 (the chunked
-                                                        matrix-core form of csrc/wkv_chunk.hip), the two forms alternating three times, warm and cold
-    python scripts/ubench/rwkv_bench.py sweep           the same A/B over token counts from 128 upward, warm: what MI_WKV_CHUNK_MIN_TOKENS rests on
+    python scripts/ubench/rwkv_bench.py chunk [OP ..]   WKV6, GLA and WKV7 (or the ops named) at the prompt shapes, each under wkv_chunk 0 (the serial kernels of
+                                                        csrc/rwkv.hip) and 2 (the chunked matrix-core forms of csrc/wkv_chunk.hip and csrc/wkv7_chunk.hip), the two
+                                                        forms alternating three times, warm and cold
+    python scripts/ubench/rwkv_bench.py sweep [OP ..]   the same A/B over token counts from 128 upward, warm: what MI_WKV_CHUNK_MIN_TOKENS and
+                                                        MI_WKV7_CHUNK_MIN_TOKENS rest on
 
 warm: one operand set, launched again and again (a one-sequence state of 1 - 2.6 MB stays in the L2 / the 256 MiB Infinity Cache).  cold: `copies` operand sets of
 more than 512 MiB together, one launch each per graph, so that no launch finds its state in a cache.  Every case is warmed up before its timed window; a
@@ -112,11 +114,14 @@ def main():
             measure(be, sys.argv[1], sys.argv[2], sys.argv[3], mode)
         be.close()
         return 0
-    if len(sys.argv) == 2 and sys.argv[1] in ("chunk", "sweep"):
+    if len(sys.argv) >= 2 and sys.argv[1] in ("chunk", "sweep") and all(op in OPS for op in sys.argv[2:]):
         be = L.Backend(0)
         be.set_option("graphs", 0)
-        for model in ("rwkv6-7b", "qrwkv6-32b"):
-            for op in ("wkv6", "gla"):
+        # WKV6 and GLA at 64 heads of 64 and 40 of 128; WKV7 at RWKV-7-2.9B's 40 heads of 64 and at 40 of 128
+        for model in ("rwkv6-7b", "rwkv7-2.9b", "qrwkv6-32b"):
+            for op in (sys.argv[2:] or list(OPS)):
+                if model == ("rwkv6-7b" if op == "wkv7" else "rwkv7-2.9b"):
+                    continue
                 for shape in (CHUNK_SHAPES if sys.argv[1] == "chunk" else SWEEP_SHAPES):
                     for mode in (("warm", "cold") if sys.argv[1] == "chunk" else ("warm",)):
                         for chunk in (0, 2) * (3 if sys.argv[1] == "chunk" else 2):
